@@ -250,6 +250,63 @@ def test_dasm_head_finish_bwd_and_sup_loss_vs_torch():
         assert float((grad.cpu().double() - pd.grad)[fin].abs().max()) < 1e-4 * float(pd.grad[fin].abs().max()), (kind, gp, gn, margin)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("layout", ["contiguous", "transposed"])
+def test_supervised_loss_dtypes_and_layouts_vs_float64_autograd(dtype, layout):
+    """The drop-in loss (dasm_trainer.loss_function_factory) as the trainers call it: f32 / f16 / bf16 posteriors, contiguous or a
+    transposed view, exact 0 and 1 among them (torch clamps the log at -100) -- loss and gradient against torch autograd in float64 on the
+    same (rounded) values; the gradient comes back in the prediction's dtype and layout."""
+    from transformer4sed_amd.dasm_trainer import loss_function_factory
+    g = torch.Generator().manual_seed(23)
+    B, C, T = 2, 8, 256
+    pr = torch.rand(B, T, C, generator=g).clamp(1e-7, 1.0)
+    pr[0, :4, 0] = torch.tensor([0.0, 1.0, 1e-7, 0.5])
+    pr[1, :4, 1] = torch.tensor([1.0, 0.0, 1.0 - 2 ** -12, 0.5])
+    tg = (torch.rand(B, C, T, generator=g) < 0.3).float()
+    tg[1, 3, 100:150] = torch.rand(50, generator=g)          # soft labels (mixup)
+    tg[0, 0, 0], tg[0, 0, 1], tg[1, 1, 0], tg[1, 1, 1] = 1.0, 0.0, 0.0, 1.0      # saturated edges with and against the target
+    pr = pr.to(dtype)
+    base = pr.transpose(1, 2) if layout == "transposed" else pr.transpose(1, 2).contiguous()       # [B, C, T]
+    eps = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}[dtype]
+    for name, kw, formula in (("BCELoss", None, "bce"), ("MSELoss", {}, "mse"), ("AsymmetricalFocalLoss", dict(gamma=1.0, zeta=2.0), "asl"),
+                              ("AslLoss", dict(rp=0.5, rn=4.0, margin=0.05), "asl")):
+        fn = loss_function_factory(name, kw)
+        pred = base.to(DEV).detach().requires_grad_(True)
+        if layout == "transposed":
+            assert not pred.is_contiguous()
+        loss = fn(pred, tg.to(DEV))
+        loss.backward()
+        pd = base.double().detach().requires_grad_(True)
+        t64 = tg.double()
+        if formula == "mse":
+            want = torch.nn.functional.mse_loss(pd, t64)
+        elif formula == "bce":
+            want = torch.nn.functional.binary_cross_entropy(pd, t64)
+        else:
+            gp, gn, mg = (kw["gamma"], kw["zeta"], 0.0) if name == "AsymmetricalFocalLoss" else (kw["rp"], kw["rn"], kw["margin"])
+            pm_ = torch.maximum(pd - mg, torch.zeros_like(pd))
+            want = torch.mean(-(((1 - pd) ** gp) * t64 * torch.clamp_min(torch.log(pd), -100) +
+                                (pm_ ** gn) * (1 - t64) * torch.clamp_min(torch.log(1 - pm_), -100)))
+        want.backward()
+        assert abs(float(loss) - float(want)) < 2e-5 * max(1.0, abs(float(want))), (name, dtype, layout, float(loss), float(want))
+        assert pred.grad is not None and pred.grad.dtype == dtype and pred.grad.shape == pred.shape, (name, dtype, layout)
+        got, ref = pred.grad.cpu().double(), pd.grad
+        fin = torch.isfinite(ref) & (ref.abs() < 1e6)      # (torch's BCE gradient at p = 0 or 1 is 1 / max(p (1 - p), 1e-12): not a number to match)
+        tol = 1e-4 * float(ref[fin].abs().max()) + 2 * eps * ref[fin].abs()
+        bad = ((got - ref)[fin].abs() > tol)
+        assert not bool(bad.any()), (name, dtype, layout, float((got - ref)[fin].abs().max()))
+    # no gradient wanted: the value alone
+    with torch.no_grad():
+        v = loss_function_factory("BCELoss", None)(base.to(DEV), tg.to(DEV))
+    assert abs(float(v) - float(torch.nn.functional.binary_cross_entropy(base.double(), tg.double()))) < 2e-5 * max(1.0, float(v))
+    # keyword arguments that would change the result are refused; the defaults the YAMLs may spell out are not
+    loss_function_factory("BCELoss", dict(reduction="mean"))
+    for name, kw in (("BCELoss", dict(reduction="sum")), ("MSELoss", dict(reduction="none")), ("BCELoss", dict(weight=torch.ones(3))),
+                     ("AslLoss", dict(rp=1, rn=1, margin=0, weight=[1.0]))):
+        with pytest.raises((NotImplementedError, TypeError)):
+            loss_function_factory(name, kw)
+
+
 def test_wide_classifier_head_407_classes_vs_torch():
     """The closed-set head at the AudioSet-Strong class count (recipes/audioset_strong/base/passt_cnn; passt_cnn.py:74-86): forward and
     backward of classifier + sigmoid / temperature + pad mask + linear-softmax pooling."""

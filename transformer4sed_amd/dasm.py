@@ -144,7 +144,10 @@ class DasmHead:
         """[K_0 | V_0 | K_1 | V_1 | ...] projections of the patch tokens with the at_projector folded in:
         k_l = W_k,l (W_at x + b_at) + b_k,l = (W_k,l W_at) x + (W_k,l b_at + b_k,l)   -- fp32 products on the device.  -> (w, b, wkv)."""
         Dd, P = self.Dd, self.P
-        key = tuple(P(f"at_decoder.decoder.layers.{l}.multihead_attn.in_proj_weight").data_ptr() for l in range(self.L)) + (P("at_projector.weight").data_ptr(), self.generation())
+        # every tensor the fold reads, by (storage, version): in-place writers (torch.optim.AdamW in all three forms, p.copy_ under
+        # no_grad, a sub-module's load_state_dict) keep data_ptr and only move `_version`; raw-pointer writers bump the generation
+        names = [f"at_decoder.decoder.layers.{l}.multihead_attn.in_proj_{s}" for l in range(self.L) for s in ("weight", "bias")]
+        key = tuple((t.data_ptr(), t._version) for t in map(P, names + ["at_projector.weight", "at_projector.bias"])) + (self.generation(),)
         if not cache or self._fused is None or self._fused_key != key:
             wkv = torch.cat([P(f"at_decoder.decoder.layers.{l}.multihead_attn.in_proj_weight")[Dd:] for l in range(self.L)], 0).contiguous()
             bkv = torch.cat([P(f"at_decoder.decoder.layers.{l}.multihead_attn.in_proj_bias")[Dd:] for l in range(self.L)], 0).contiguous()

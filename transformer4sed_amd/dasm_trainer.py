@@ -31,12 +31,15 @@ class SupervisedLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, kind, gamma_pos, gamma_neg, margin):
-        pred = pred.contiguous()
+        # (pred arrives contiguous fp32: `_Loss.__call__` makes it so outside this Function, where autograd records the cast and the copy;
+        #  grad mode is off in here, so `requires_grad` of a tensor made here says nothing -- `needs_input_grad` does)
+        if pred.dtype != torch.float32 or not pred.is_contiguous():
+            raise ValueError("SupervisedLoss: the prediction must be a contiguous float32 tensor")
         target = target.contiguous().float()
         if pred.shape != target.shape:
             raise ValueError(f"prediction {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
         loss = torch.zeros(1, dtype=torch.float32, device=pred.device)
-        grad = torch.empty_like(pred) if pred.requires_grad else None
+        grad = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
         call("sed_sup_loss", pred, target, loss, grad, pred.numel(), int(kind), float(gamma_pos), float(gamma_neg), float(margin))
         ctx.save_for_backward(grad)
         return loss[0]
@@ -53,19 +56,26 @@ class _Loss:
 
     def __call__(self, input=None, target=None, **kw):
         pred = input if input is not None else kw.get("pred")
-        return SupervisedLoss.apply(pred, target, *self.args)
+        return SupervisedLoss.apply(pred.float().contiguous(), target, *self.args)
 
     def to(self, device):       # (the recipes call `.to(device)` on the loss module)
         return self
 
 
 def loss_function_factory(name, kwargs=None):
-    """src/functional/loss/__init__.py:18-22 for the elementwise losses of that module."""
+    """src/functional/loss/__init__.py:18-22 for the elementwise losses of that module.  Keyword arguments the kernel does not implement
+    raise instead of being dropped: torch's BCELoss / MSELoss take only their defaults (mean reduction, no weight), the two asymmetric
+    losses exactly their constructor arguments (the reference raises a TypeError on any other key too)."""
     kw = dict(kwargs or {})
-    if name == "BCELoss":
-        return _Loss()
-    if name == "MSELoss":
-        return _Loss(kind=1)
+    if name in ("BCELoss", "MSELoss"):
+        defaults = dict(weight=None, size_average=None, reduce=None, reduction="mean")
+        bad = {k: v for k, v in kw.items() if k not in defaults or not (v == defaults[k] or (k in ("size_average", "reduce") and v is True))}
+        if bad:
+            raise NotImplementedError(f"class_loss {name}: the HIP loss is the unweighted mean; unsupported kwargs {bad}")
+        return _Loss(kind=0 if name == "BCELoss" else 1)
+    allowed = {"AsymmetricalFocalLoss": ("gamma", "zeta"), "AslLoss": ("rp", "rn", "margin")}.get(name)
+    if allowed is not None and set(kw) - set(allowed):
+        raise TypeError(f"class_loss {name}: unexpected kwargs {sorted(set(kw) - set(allowed))}")
     if name == "AsymmetricalFocalLoss":      # :59-68
         return _Loss(0, kw.get("gamma", 0), kw.get("zeta", 0), 0.0)
     if name == "AslLoss":                    # :25-37

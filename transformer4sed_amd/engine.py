@@ -12,6 +12,7 @@ autograd node so that the reference's training loops (loss via torch ops, loss.b
 import math
 
 import torch
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import ops
 import os
@@ -23,6 +24,20 @@ from .ops import EPI_F32, EPI_F32_RESID, EPI_BF16, EPI_GELU, EPI_DGELU, EPI_F32_
 D = 768
 H = 12
 NCLS_MAX = 16
+
+
+def _fused_step_moves_versions(optimizer, args, kwargs):
+    """torch.optim's fused implementations (`fused=True`: torch._fused_adamw_ and its kin) rewrite the parameters without moving their
+    version counters, unlike the foreach and for-loop forms.  The weight-image caches below key on `_version`: move it for every
+    parameter such a step updated (the ones with a gradient)."""
+    for g in optimizer.param_groups:
+        if g.get("fused"):
+            ps = [p for p in g["params"] if p.grad is not None]
+            if ps:
+                torch.autograd.graph.increment_version(ps)
+
+
+register_optimizer_step_post_hook(_fused_step_moves_versions)
 
 
 def window_starts(n_in=1000, win=512, step=49):
