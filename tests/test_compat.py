@@ -105,3 +105,28 @@ def test_reference_import_surface_resolves_through_compat(tmp_path):
     assert all(out["checkout"]), out["checkout"]
     assert out["maestro"] == "ref-maestro" and out["decoder_loaded_on_demand"] is True
     assert out["model"][0] == "PaSST_SED" and out["model"][1] is True and out["model"][2] == 100947762
+
+
+def test_update_ema_moves_every_teacher_version_with_the_data_form_arithmetic():
+    """`src.utils.update_ema` (transformer4sed_amd.scheduler.update_ema, checked above) writes the teacher's parameters in place, so each
+    one's `_version` moves -- the cached weight images key on it (engine.version_key) -- with the arithmetic of the reference's `.data`
+    form bit for bit.  The teacher's first layer is detached (the recipes' teacher), the rest still requires grad."""
+    import copy
+    import torch
+    from transformer4sed_amd.scheduler import update_ema
+    torch.manual_seed(0)
+    net = torch.nn.Sequential(torch.nn.Linear(8, 16), torch.nn.LayerNorm(16), torch.nn.Linear(16, 3))
+    ema = copy.deepcopy(net)
+    for p in ema[0].parameters():
+        p.detach_()
+    with torch.no_grad():
+        for p in net.parameters():
+            p.add_(torch.randn_like(p))
+    want = [p.detach().clone() for p in ema.parameters()]
+    alpha = min(1 - 1 / 3, 0.999)
+    for w, p in zip(want, net.parameters()):
+        w.data.mul_(alpha).add_(p.data, alpha=1 - alpha)
+    v0 = [p._version for p in ema.parameters()]
+    assert update_ema(net, ema, 3, 0.999) is ema
+    assert all(p._version > v for p, v in zip(ema.parameters(), v0))
+    assert all(torch.equal(p, w) for p, w in zip(ema.parameters(), want))

@@ -1,10 +1,11 @@
 """The derived images of the fp32 weights (engine.py `_lnf_image` / `_w2_image` / `_w2f8_image` / `_wlo_image`, the PMAM statics of
-frozen LoRA blocks, DASM's folded K / V projection) are cached between forwards and rebuilt only when their key moves.  Every write a
-training script can make to the masters -- torch.optim.AdamW (foreach, for-loop, fused), `p.copy_` under no_grad, load_state_dict of
-the model / of a sub-module / through the compat DataParallelWrapper, the compat `update_ema`, the recipes' freeze / unfreeze sequence --
-must show in the next forward: forward, write, forward again must equal a FRESH model loaded with the written weights (same kernels,
-same weights: bit level) and differ from the first forward.  White box: every populated cache slot whose masters the write touched got
-a new key, every other slot kept its own (frozen images survive optimiser steps)."""
+frozen LoRA blocks, DASM's folded K / V projection) are cached between forwards and rebuilt only when their key (engine.version_key)
+moves.  Every write a training script can make to the masters -- torch.optim.AdamW (foreach, for-loop, fused), trainer.FusedAdamWEMA
+(student, EMA teacher), `p.copy_` under no_grad, load_state_dict of the model / of a sub-module / through the compat
+DataParallelWrapper, the compat `update_ema`, the recipes' freeze / unfreeze sequence -- must show in the next forward: forward, write,
+forward again must equal a FRESH model loaded with the written weights (same kernels, same weights: bit level) and differ from the first
+forward.  White box: every populated cache slot whose masters the write touched got a new key, every other slot kept its own (frozen
+images survive optimiser steps)."""
 import os
 import sys
 
@@ -141,8 +142,9 @@ def slots(net):
         if not any(pbn[d].requires_grad for d in deps(net, ("static", n))):
             out[("static", n)] = k
     head = getattr(net, "dasm_head", None)
-    if head is not None and head._fused_key is not None:
-        out[("fold", "dasm")] = head._fused_key
+    for s in ("_fused_key", "_fused_split_key"):
+        if head is not None and getattr(head, s) is not None:
+            out[(s, "dasm")] = getattr(head, s)
     return out
 
 
@@ -158,18 +160,18 @@ def deps(net, slot):
     if kind == "static":
         spec = next(sp for sp in net.engine._specs[0] if sp[0] == n)
         return {spec[1], spec[5] + ".lora_A", spec[5] + ".lora_B"}
-    L = net.dasm_head.L
+    L = net.dasm_head.L          # (the DASM head's fold and its split image)
     return {f"at_decoder.decoder.layers.{l}.multihead_attn.in_proj_{s}" for l in range(L) for s in ("weight", "bias")} | \
         {"at_projector.weight", "at_projector.bias"}
 
 
-def check_slots(net, s0, s1, written, what, toggled=(), reach=True):
-    """`toggled`: masters whose requires_grad flag changed -- the images built from them may be re-keyed without a write (engine._gen).
-    `reach`: the write must reach at least one cached image (False: a write to tensors without cached images -- nothing may be rebuilt)."""
+def check_slots(net, s0, s1, written, what, reach=True):
+    """`reach`: the write must reach at least one cached image (False: a write to tensors without cached images -- nothing may be
+    rebuilt).  A requires_grad flip is no write: it re-keys nothing."""
     assert s0, f"{what}: no cached image populated -- the forward ran a path without a cache"
     lost = {k for k in set(s0) - set(s1) if k[0] != "static"}      # (a PMAM statics entry leaves the set while its block trains)
     assert not lost, f"{what}: slots vanished {sorted(lost)}"
-    common = {k for k in set(s0) & set(s1) if not (deps(net, k) & set(toggled) and not deps(net, k) & written)}
+    common = set(s0) & set(s1)
     changed = {k for k in common if s0[k] != s1[k]}
     expect = {k for k in common if deps(net, k) & written}
     assert expect or not reach, f"{what}: the write reaches no cached image"
@@ -260,9 +262,12 @@ def fresh_like(kind, net):
     return fresh
 
 
-def run_case(kind, fwd, write, what, reach=True):
-    """before = fwd(net); written = write(net, groups); after = fwd(net) == fwd(fresh model with net's state) and != before."""
+def run_case(kind, fwd, write, what, reach=True, setup=None):
+    """before = fwd(net); written = write(net, groups); after = fwd(net) == fwd(fresh model with net's state) and != before.  `setup(net,
+    groups)`, before the first forward, replaces `groups` with what `write` needs."""
     net, groups = BUILD[kind]()
+    if setup is not None:
+        groups = setup(net, groups)
     f = FWD[fwd]
     f(net)
     before = f(net)
@@ -316,6 +321,51 @@ def test_dasm_after_adamw_vs_float64_oracle():
            f"(strong {es:.3e} weak {ew:.3e} at {ea:.3e})")
     assert maxerr(after, before) > MOVED
     assert es < 1e-4 and ew < 1e-4 and ea < 1e-5, (es, ew, ea)
+
+
+# ---------------------------------------------------------------------------------------------------------------- (a') FusedAdamWEMA
+def fused_opt(student, groups, teacher=None):
+    """trainer.FusedAdamWEMA: binds the masters into its arena, so it is built before the first forward (`run_case(setup=...)`)."""
+    from transformer4sed_amd.trainer import FusedAdamWEMA
+    return FusedAdamWEMA(student, groups, ema_net=teacher)
+
+
+def fused_step(opt, seed, ema_alpha=None):
+    """Random gradients for the student's trainable parameters, laid out in the optimiser's arena as the model's backward lays them out
+    (passt_sed._SedFunction.backward), and one FusedAdamWEMA step; -> the student parameters it stepped."""
+    net, g = opt.net, torch.Generator(device=DEV).manual_seed(seed)
+    arena = torch.zeros(opt.total, dtype=torch.float32, device=DEV)
+    byname = dict(net.named_parameters())
+    for n, p in byname.items():
+        if p.requires_grad and n not in net._inert_param_names:
+            o, k = opt.offset[n]
+            arena[o:o + k].copy_(torch.randn(k, generator=g, device=DEV))
+            p.grad = arena[o:o + k].view(p.shape)
+    net._last_grad_arena = arena
+    opt.step(ema_alpha)
+    written = {n for g_ in opt.param_groups for n in g_["names"] if byname[n].grad is not None}
+    opt.zero_grad()
+    return written
+
+
+@pytest.mark.parametrize("kind,fwd", ADAMW_CASES)
+def test_fused_adamw_ema_student_step(kind, fwd):
+    run_case(kind, fwd, lambda net, opt: fused_step(opt, 41), "FusedAdamWEMA.step (student)", reach=kind != "pmam", setup=fused_opt)
+
+
+@pytest.mark.parametrize("kind,fwd", [("teacher", "train_nograd"), ("teacher", "eval_win"), ("pmam", "eval")])
+def test_fused_adamw_ema_teacher_sweep(kind, fwd):
+    """MatSedTrainer's step: AdamW on a (perturbed) student, then the EMA sweep rewrites every tensor of the teacher whatever its
+    requires_grad says -- MAT-SED's detached teacher, PMAM's frozen LoRA block (statics)."""
+    def setup(teacher, _):
+        student, groups = BUILD["matsed" if kind == "teacher" else kind]()
+        student.load_state_dict(_perturbed_state(student, 43), strict=True)
+        return fused_opt(student, groups, teacher)
+
+    def write(teacher, opt):
+        fused_step(opt, 47, ema_alpha=0.5)
+        return set(teacher._param_by_name)
+    run_case(kind, fwd, write, "FusedAdamWEMA.step (EMA teacher)", setup=setup)
 
 
 # ---------------------------------------------------------------------------------------------------------------- (b) p.copy_
@@ -415,7 +465,7 @@ def test_freeze_unfreeze_sequence(kind, fwd, block):
     want2 = f(fresh_like(kind, net))
     for step, (a, b, want, sa, sb, w) in enumerate(((out0, out1, want1, s0, s1, written), (out1, out2, want2, s1, s2, written2))):
         what = f"freeze / unfreeze {block} step {step + 1}"
-        n_hit, n_all = check_slots(net, sa, sb, w, what, toggled=set(blk), reach=kind != "pmam" or step == 0)
+        n_hit, n_all = check_slots(net, sa, sb, w, what, reach=kind != "pmam" or step == 0)
         moved, err = maxerr(b, a), maxerr(b, want)
         report(f"{kind} / {fwd} / {what}", moved, err, f"(slots rebuilt {n_hit} of {n_all})")
         assert moved > MOVED, (what, moved)

@@ -20,6 +20,7 @@ at_projector folded into their weights (W_kv . W_at: one GEMM over the 1188 toke
 gradient of the folded weight into the gradients of its two factors (two small GEMMs)."""
 import torch
 
+from .engine import cached_image
 from .ops import call, h2d
 
 F32 = torch.float32
@@ -118,10 +119,7 @@ class DasmHead:
             raise NotImplementedError("head_dim must be 32 or 64")
         self.L, self.H, self.Dd, self.dh = n_layers, num_heads, decoder_dim, decoder_dim // num_heads
         self.dropout = float(dropout)
-        self._fused = self._fused_split = None
-        self._fused_key = None
-        self.generation = lambda: 0      # (the whole model: its parameter generation -- in-place writers do not move data_ptr)
-        self._set_params(params)
+        self.refresh(params)
 
     def _set_params(self, params):
         if callable(params):
@@ -135,27 +133,32 @@ class DasmHead:
         return self._get(name)
 
     def refresh(self, params=None):
-        """Call after the weights changed (the folded memory projection is cached between no-grad passes)."""
+        """Re-bind the head to `params` (a standalone parameter dict) and drop the images cached across forwards (engine.cached_image: the
+        folded memory projection `_fused` and its split image, keyed on their sources' versions)."""
         if params is not None:
             self._set_params(params)
-        self._fused = self._fused_split = self._fused_key = None
+        self._fused = self._fused_key = self._fused_split = self._fused_split_key = None
 
     def _memory_weights(self, cache=True):
         """[K_0 | V_0 | K_1 | V_1 | ...] projections of the patch tokens with the at_projector folded in:
         k_l = W_k,l (W_at x + b_at) + b_k,l = (W_k,l W_at) x + (W_k,l b_at + b_k,l)   -- fp32 products on the device.  -> (w, b, wkv)."""
         Dd, P = self.Dd, self.P
-        # every tensor the fold reads, by (storage, version): in-place writers (torch.optim.AdamW in all three forms, p.copy_ under
-        # no_grad, a sub-module's load_state_dict) keep data_ptr and only move `_version`; raw-pointer writers bump the generation
-        names = [f"at_decoder.decoder.layers.{l}.multihead_attn.in_proj_{s}" for l in range(self.L) for s in ("weight", "bias")]
-        key = tuple((t.data_ptr(), t._version) for t in map(P, names + ["at_projector.weight", "at_projector.bias"])) + (self.generation(),)
-        if not cache or self._fused is None or self._fused_key != key:
+
+        def build():
             wkv = torch.cat([P(f"at_decoder.decoder.layers.{l}.multihead_attn.in_proj_weight")[Dd:] for l in range(self.L)], 0).contiguous()
             bkv = torch.cat([P(f"at_decoder.decoder.layers.{l}.multihead_attn.in_proj_bias")[Dd:] for l in range(self.L)], 0).contiguous()
             wat_t = P("at_projector.weight").t().contiguous()                       # [768 (in), Dd]: B operand rows = output columns
             w = gemm_f32(wkv, wat_t)                                                # [2 L Dd, 768]
             b = gemm_f32(P("at_projector.bias").view(1, Dd), wkv, bias=bkv).view(-1)
-            self._fused, self._fused_key, self._fused_split = (w, b, wkv), key, None
-        return self._fused
+            return w, b, wkv
+        if not cache:
+            self.refresh()
+        return cached_image(self, "_fused", self._fold_sources(), build)
+
+    def _fold_sources(self):
+        """Every tensor the folded memory projection reads."""
+        names = [f"at_decoder.decoder.layers.{l}.multihead_attn.in_proj_{s}" for l in range(self.L) for s in ("weight", "bias")]
+        return [self.P(n) for n in names + ["at_projector.weight", "at_projector.bias"]]
 
     # ------------------------------------------------------------------ Linear layers: fp32 MFMA, or the 16-bit matrix pipe when large
     @staticmethod
@@ -306,11 +309,10 @@ class DasmHead:
             # tokens and of the folded weight, x_hi W_hi + x_lo W_hi + x_hi W_lo accumulated in fp32 (the context network's form,
             # ~2^-20 of the product) -- 3 x the f16 FLOPs at ~10 x the fp32-MFMA rate
             from . import ops
-            if save or self._fused_split is None or self._fused_split.device != dev:
-                self._fused_split = ops.split3(wkv, ldkv, Din, weight=True)
+            wsplit = cached_image(self, "_fused_split", self._fold_sources(), lambda: ops.split3(wkv, ldkv, Din, weight=True))
             KV = E(B * Pn, ldkv)
             with ops.split_precision():
-                ops.gemm_nt(ops.split3(ft2, B * Pn, Din), self._fused_split, ops.EPI_F32, bias=bkv, outF=KV)
+                ops.gemm_nt(ops.split3(ft2, B * Pn, Din), wsplit, ops.EPI_F32, bias=bkv, outF=KV)
         else:
             KV = gemm_f32(ft2, wkv, bias=bkv)          # [B P, 2 L Dd]
         # ---- queries (detect_any_sound.py:266-289): nn.Linear + GELU on the embeddings
@@ -607,7 +609,6 @@ class DASM(PaSST_CNN):
         self.sed_head = nn.Linear(Dd, Dd)
         self.merge_weight.requires_grad_(False)    # (detect_any_sound.py:73: trainable only with an mlm_dict)
         self.dasm_head = DasmHead(self._head_param, self.at_layers, num_heads, decoder_dim, dropout=self.at_dropout)
-        self.dasm_head.generation = self._head_generation
         self.__dict__["_dasm_call"] = dict(query=None, tgt_mask=None, query_type=None)      # (plain dict: a ParameterList here must not become a child module)
         self._dasm_external_query = False
         self._drop_gen = None
@@ -634,13 +635,9 @@ class DASM(PaSST_CNN):
                 if tail.startswith(ref):
                     state_dict[prefix + mine + tail[len(ref):]] = state_dict.pop(key)
                     break
-        module.dasm_head.refresh()
 
     def _head_param(self, name):
         return self._param_by_name[name].detach()
-
-    def _head_generation(self):
-        return getattr(self, "_param_generation", 0)
 
     def _next_drop_seed(self):
         """Seed of one train-mode forward's dropout bits: drawn from a generator private to this model (seeded from torch.initial_seed() on

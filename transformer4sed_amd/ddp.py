@@ -56,8 +56,6 @@ def broadcast_buffers(net, src=0, group=None):
         for b in bufs:
             b.copy_(flat[off:off + b.numel()].view(b.shape).to(b.dtype))
             off += b.numel()
-    if hasattr(net, "_param_generation"):
-        net._param_generation += 1
     return len(bufs)
 
 

@@ -26,10 +26,27 @@ H = 12
 NCLS_MAX = 16
 
 
+def version_key(sources, form=None):
+    """Cache key of an image derived from the tensors `sources`: (device, data_ptr, _version) of each, plus a form tag.  The one rule of
+    every cached weight image: it is rebuilt iff the storage or the version of one of its sources moved.  torch moves `_version` on every
+    in-place write (optimisers, `copy_`, load_state_dict); the project's raw-pointer writers (FusedAdamWEMA, update_ema) move it
+    themselves with torch.autograd.graph.increment_version."""
+    return tuple((t.device, t.data_ptr(), t._version) for t in sources) + (form,)
+
+
+def cached_image(holder, slot, sources, build, form=None):
+    """`holder.<slot>`, rebuilt with `build()` when the `version_key` of `sources` / `form` differs from `holder.<slot>_key`."""
+    key = version_key(sources, form)
+    if getattr(holder, slot + "_key") != key:
+        setattr(holder, slot, build())
+        setattr(holder, slot + "_key", key)
+    return getattr(holder, slot)
+
+
 def _fused_step_moves_versions(optimizer, args, kwargs):
     """torch.optim's fused implementations (`fused=True`: torch._fused_adamw_ and its kin) rewrite the parameters without moving their
-    version counters, unlike the foreach and for-loop forms.  The weight-image caches below key on `_version`: move it for every
-    parameter such a step updated (the ones with a gradient)."""
+    version counters, unlike the foreach and for-loop forms.  The weight-image caches key on `_version` (`version_key`): move it for
+    every parameter such a step updated (the ones with a gradient)."""
     for g in optimizer.param_groups:
         if g.get("fused"):
             ps = [p for p in g["params"] if p.grad is not None]
@@ -60,14 +77,13 @@ def rel_pos_table(T, Dm=D):
 
 
 class _W:
-    """bf16 operand images of one fp32 weight matrix [n_out, k_in]."""
+    """bf16 operand images of one fp32 weight matrix [n_out, k_in] (rewritten by every forward), and the images cached across forwards
+    (`cached_image`): LayerNorm-folded `lnf`, two-term `w2` (f16 or fp8 form), residual `wlo`, each beside its key."""
     __slots__ = ("w", "wt", "ws", "wlo", "wlo_key", "w2", "w2_key", "lnf", "lnf_key")
 
     def __init__(self, w, wt):
         self.w, self.wt, self.ws = w, wt, None
-        self.wlo, self.wlo_key = None, None      # f16 image of 2^11 (W - f16(W)) (evaluation-mode mean correction) and what it was built from
-        self.w2, self.w2_key = None, None        # two-term image [f16(W) | f16(W - f16(W))] (evaluation-mode encoder)
-        self.lnf, self.lnf_key = None, None      # LayerNorm-folded image (f16(gamma . W), colS, colC) (no-grad encoder passes)
+        self.wlo = self.wlo_key = self.w2 = self.w2_key = self.lnf = self.lnf_key = None
 
 
 class _PoolLease:
@@ -172,65 +188,41 @@ class SedEngine:
             return False        # PaSST_CNN in train mode: the GEMM operand is W + s B A, not the master the residual image is taken from
         return self.wcorr_all or not self.m.training
 
-    def _gen(self, *names):
-        """Cache-key component for images of the fp32 masters `names`: the module's parameter generation (bumped by the raw-pointer
-        writers: fused AdamW on the student, the EMA sweep on the teacher) -- but only when one of them can actually be written: frozen
-        (`requires_grad` off) and inert (lr-0 group) tensors never change under the optimiser, so their images survive its steps."""
-        inert = getattr(self.m, "_inert_param_names", ())
-        ema_written = getattr(self.m, "_ema_written", False)      # the EMA sweep rewrites EVERY tensor of a teacher
-        if ema_written or any(self.P(n).requires_grad and n not in inert for n in names):
-            return getattr(self.m, "_param_generation", 0)
-        return 0
-
     def _lnf_image(self, W, wname, bname, gname, btname):
-        """(f16(gamma (.) W), colS, colC) of a Linear that follows a LayerNorm (sed_ln_fold_weight), cached per weight: rebuilt when
-        any of the four masters changed."""
-        ent = W[wname]
-        ps = [self.P(n) for n in (wname, bname, gname, btname)]
-        key = tuple((p.data_ptr(), p._version) for p in ps) + (self._gen(wname, bname, gname, btname),)
-        if ent.lnf is None or ent.lnf_key != key or ent.lnf[0].device != ent.w.device:
-            n_out, k_in = ent.w.shape
-            w16 = torch.empty(n_out, k_in, dtype=F16, device=ent.w.device)
-            cs, cc = torch.empty(n_out, device=ent.w.device), torch.empty(n_out, device=ent.w.device)
-            call("sed_ln_fold_weight", ps[0].detach().reshape(n_out, k_in).contiguous(), ps[2].detach(), ps[3].detach(), ps[1].detach(),
+        """(f16(gamma (.) W), colS, colC) of a Linear that follows a LayerNorm (sed_ln_fold_weight), cached per weight on all four
+        masters."""
+        w, b, g, bt = ps = [self.P(n) for n in (wname, bname, gname, btname)]
+
+        def build():
+            n_out, k_in = W[wname].w.shape
+            w16 = torch.empty(n_out, k_in, dtype=F16, device=w.device)
+            cs, cc = torch.empty(n_out, device=w.device), torch.empty(n_out, device=w.device)
+            call("sed_ln_fold_weight", w.detach().reshape(n_out, k_in).contiguous(), g.detach(), bt.detach(), b.detach(),
                  w16, cs, cc, n_out, k_in)
-            ent.lnf, ent.lnf_key = (w16, cs, cc), key
-        return ent.lnf
+            return w16, cs, cc
+        return cached_image(W[wname], "lnf", ps, build)
 
     def _w2_image(self, W, name):
-        """Two-term f16 image [n_out, 2 k_in] of an fp32 weight, cached per weight like `_wlo_image`."""
-        ent = W[name]
+        """Two-term f16 image [n_out, 2 k_in] of an fp32 weight, cached per weight."""
         p = self.P(name)
-        key = (p.data_ptr(), p._version, self._gen(name), "f16")
-        if ent.w2 is None or ent.w2_key != key or ent.w2.device != ent.w.device:
-            ent.w2 = two_term_weight(p.detach().reshape(ent.w.shape))
-            ent.w2_key = key
-        return ent.w2
+        return cached_image(W[name], "w2", [p], lambda: two_term_weight(p.detach().reshape(W[name].w.shape)), "f16")
 
     def _w2f8_image(self, W, name):
         """(uint8 image [n_out, 3 k_in] = rows [f16(W) | e4m3(2^s (W - f16(W)))], s) of an fp32 weight, cached like `_w2_image` (same slot:
         a module runs one of the two forms)."""
-        ent = W[name]
         p = self.P(name)
-        key = (p.data_ptr(), p._version, self._gen(name), "f8")
-        if ent.w2 is None or ent.w2_key != key or ent.w2[0].device != ent.w.device:
-            ent.w2 = two_term_weight_f8(p.detach().reshape(ent.w.shape))
-            ent.w2_key = key
-        return ent.w2
+        return cached_image(W[name], "w2", [p], lambda: two_term_weight_f8(p.detach().reshape(W[name].w.shape)), "f8")
 
-    def _wlo_image(self, W, name, w32=None):
-        """f16 image of 2^11 (W - f16(W)), cached per weight: rebuilt when the fp32 master changed (in-place writes move `_version`,
-        raw-pointer writers -- fused AdamW / EMA -- bump the module's parameter generation)."""
-        ent = W[name]
+    def _wlo_image(self, W, name):
+        """f16 image of 2^11 (W - f16(W)), cached per weight."""
         p = self.P(name)
-        key = (p.data_ptr(), p._version, self._gen(name), id(w32) if w32 is not None else 0)
-        if ent.wlo is None or ent.wlo_key != key or ent.wlo.device != ent.w.device:
-            src = (w32 if w32 is not None else p.detach()).reshape(ent.w.shape).contiguous()
-            if ent.wlo is None or ent.wlo.shape != ent.w.shape or ent.wlo.device != ent.w.device:
-                ent.wlo = torch.empty(ent.w.shape, dtype=F16, device=ent.w.device)
-            call("sed_weight_residual_f16", src, ent.wlo, src.numel(), 2048.0)
-            ent.wlo_key = key
-        return ent.wlo
+
+        def build():
+            src = p.detach().reshape(W[name].w.shape).contiguous()
+            wlo = torch.empty(src.shape, dtype=F16, device=src.device)
+            call("sed_weight_residual_f16", src, wlo, src.numel(), 2048.0)
+            return wlo
+        return cached_image(W[name], "wlo", [p], build)
 
     def _wcorr_bias(self, W, name, x16, groups, rows, ld=None):
         """Row-group bias [groups, n_out] = mean over the `rows` tokens of each clip of x16 . (W - f16(W))^T (fp32).  `ld`: row pitch of

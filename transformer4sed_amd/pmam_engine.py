@@ -20,7 +20,7 @@ import torch
 
 from . import ops
 
-from .engine import SedEngine, _W, D, H
+from .engine import SedEngine, _W, D, H, version_key
 from .ops import BF16, F16, F32, call, h2d, gemm_nt, gemm_nt_cols, gemm_dw, gemm_dw_tn, dw_tn_ok, pad64, transpose_bf16, split3, is_f16, to_bf16_, o_kind
 from .ops import EPI_F32, EPI_F32_RESID, EPI_BF16, EPI_GELU32
 
@@ -203,11 +203,8 @@ class PmamEngine(SedEngine):
                     m.lora_r if use_lora else 0, sbits if use_lora else 0, 0, 0]
 
         # Frozen operands (the blocks below `freeze_layer`, cnn_trans/setting.py:66-82) keep their images across steps.  A tensor without
-        # requires_grad is not necessarily constant: the EMA teacher's masters are rewritten through raw pointers (fused AdamW + EMA
-        # kernel) or `.data` in-place ops (update_ema), neither of which moves `_version` -- so the key carries the module's parameter
-        # generation (`_gen`: bumped by every such writer and by load_state_dict; it only counts for tensors the optimiser or the EMA
-        # sweep can reach, a frozen master of the student is not re-imaged after every step) -- and `_version`, which catches the rest:
-        # sub-module load_state_dict, nn.DataParallel(net).load_state_dict, p.copy_ under no_grad.
+        # requires_grad is not necessarily constant (the EMA teacher's masters, load_state_dict, p.copy_): like every cached weight image,
+        # a block's statics are rebuilt iff the storage or the version of one of its masters moved (engine.version_key).
         live, stale = [], []
         for spec in mats:
             name, master, R, C, plan, lora, split, kind = spec
@@ -218,8 +215,7 @@ class PmamEngine(SedEngine):
             if any(p.requires_grad for p in parts):
                 live.append(spec)
                 continue
-            key = (merged, bool(need_t), self.act, tuple(p.data_ptr() for p in parts), tuple(p._version for p in parts),
-                   self._gen(master, lora + ".lora_A", lora + ".lora_B"))
+            key = version_key(parts, (merged, bool(need_t), self.act))
             if statics.get(name) != key or name not in self.cache:
                 stale.append(spec)
                 statics[name] = key

@@ -101,7 +101,7 @@ class FusedAdamWEMA:
         self.arena = torch.zeros(off, dtype=torch.float32, device=dev)
         self.m = torch.zeros(off, dtype=torch.float32, device=dev)
         self.v = torch.zeros(off, dtype=torch.float32, device=dev)
-        byname = dict(net.named_parameters())
+        self._params = byname = dict(net.named_parameters())      # (the parameters bound into the arena)
         with torch.no_grad():
             for n, o, k in layout:
                 p = byname[n]
@@ -116,6 +116,7 @@ class FusedAdamWEMA:
                     p = eby[n]
                     self.ema_arena[o:o + k].copy_(p.detach().reshape(-1))
                     p.data = self.ema_arena[o:o + k].view(p.shape)
+            self._ema_params = list(eby.values())
         net._flat_layout = self  # the model's backward lays its gradient arena out identically
         self.grad_arena = None
         self.inert_names = frozenset(n for g in self.param_groups if skip_zero_lr_groups and float(g["lr"]) == 0.0 for n in g["names"])
@@ -208,7 +209,8 @@ class FusedAdamWEMA:
             raise RuntimeError("FusedAdamWEMA: a parameter group built with lr = 0 now has a non-zero lr, but no gradients were computed "
                                "for it (construct the optimiser with skip_zero_lr_groups=False to train it later)")
         self.step_count += 1
-        touched = {n for n, p in net.named_parameters() if p.grad is not None}
+        params = self._params
+        touched = {n for n, p in params.items() if p.grad is not None}
         b1, b2 = self.betas
         done = []
         for g in self.param_groups:
@@ -218,15 +220,12 @@ class FusedAdamWEMA:
                      float(g["weight_decay"]), b1, b2, self.eps, self.step_count,
                      float(ema_alpha_value) if ema_alpha_value is not None else 0.0, 1)
                 done.append((s, e))
-        if done:
-            # the student's masters were rewritten through raw pointers too (neither `_version` nor `data_ptr` moves): the cached
-            # evaluation-mode images of its weights (two-term / residual / LayerNorm-folded, engine.py) key on this counter
-            net._param_generation = getattr(net, "_param_generation", 0) + 1
+        # the kernel writes the masters through raw pointers: move the versions the cached weight images key on (engine.version_key),
+        # of the student parameters the AdamW launches covered and, when the EMA sweep runs, of every teacher parameter
+        stepped = [params[n] for g in self.param_groups for n in g["names"] if n in touched]
+        if stepped:
+            torch.autograd.graph.increment_version(stepped)
         if self.ema_arena is not None and ema_alpha_value is not None:
-            # the teacher's masters change behind torch's back (raw-pointer kernel): engines that cache operand images of frozen
-            # tensors key them on this counter
-            self.ema_net._param_generation = getattr(self.ema_net, "_param_generation", 0) + 1
-            self.ema_net._ema_written = True          # (every tensor of the teacher moves with the sweep, whatever its requires_grad says)
             done.sort()
             pos = 0
             for s, e in done + [(self.total, self.total)]:
@@ -234,6 +233,7 @@ class FusedAdamWEMA:
                     call("sed_adamw_ema", self.arena[pos:s], self.arena[pos:s], self.m[pos:s], self.v[pos:s],
                          self.ema_arena[pos:s], s - pos, 0.0, 0.0, b1, b2, self.eps, 1, float(ema_alpha_value), 0)
                 pos = max(pos, e)
+            torch.autograd.graph.increment_version(self._ema_params)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
