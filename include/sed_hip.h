@@ -68,6 +68,22 @@ int sed_median_filter(const float* in, float* out, const int* sizes, const float
  * A window larger than max_size traps. */
 int sed_median_filter_k(const float* in, float* out, const int* sizes, const float* scale, int B, int T, int C, int mode,
                         int max_size, hipStream_t stream);
+/* Multilabel average precision, torchmetrics 0.11 MultilabelAveragePrecision with thresholds=None (the AudioSet-Strong validation metric,
+ * recipes/audioset_strong/base/passt_cnn/train.py:239-314 and the two detect_any_sound loops; csrc/metrics.hip).  Storage: scores [C][cap]
+ * f32 and labels [C][cap] uint8, class-major, caller-owned.
+ * sed_ap_append: preds / target [B,C] f32 (target 0 / 1) -> clips n0 .. n0+B-1.  If any score of the batch lies outside [0, 1] (or is NaN)
+ * the whole batch is stored as sigmoid(preds); that decision is taken on the device (flags: 64 ints of scratch).  status[0] |= 2 for a NaN
+ * score, 4 for a target outside {0, 1} (the caller zeroes it once and reads it when it computes).
+ * sed_ap_grow: copies clips 0 .. n-1 of every class into a larger storage (device to device).
+ * sed_ap_compute: ap[C] (double; NaN for a class without a positive) and npos[C] over clips 0 .. N-1.  chunk (1 .. 20000): clips per
+ * LDS sort; N <= chunk runs in one launch from LDS, otherwise all_sorted / pos_sorted (uint32 [C][ceil(N/chunk) chunk] each) hold the
+ * sorted chunks.  pos_cnt (int) and partial (uint64) [C][ceil(N/chunk)] are scratch.  The result does not depend on clip order or chunk. */
+int sed_ap_append(const float* preds, const float* target, int B, int C, int n0, int cap, int* flags, int* status, float* scores,
+                  uint8_t* labels, hipStream_t stream);
+int sed_ap_grow(const float* old_scores, const uint8_t* old_labels, int C, int n, int old_cap, float* new_scores, uint8_t* new_labels,
+                int new_cap, hipStream_t stream);
+int sed_ap_compute(const float* scores, const uint8_t* labels, int C, int N, int cap, int chunk, uint32_t* all_sorted, uint32_t* pos_sorted,
+                   int* pos_cnt, unsigned long long* partial, double* ap, int* npos, hipStream_t stream);
 
 /* ------------------------------------------------------------------ GEMM family (nn.Linear / conv / autograd GEMMs) */
 /* C[M,N] = A[M,K] . B[N,K]^T, bf16 operands, fp32 accumulate, fused epilogue `epi`:

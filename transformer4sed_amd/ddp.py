@@ -98,6 +98,7 @@ class GradBucketReducer:
         # a stage whose slices are smaller than this is not worth a collective of its own: it is carried to the next stage hook (or
         # to the end of backward) and merged with adjacent slices there
         self.min_elems = min_bytes // 4
+        self.deferred = frozenset()   # parameter names reduced only by `allreduce_grads` (see `defer`)
         self.ranges = {}
         self._flags = None
         self._build_ranges()
@@ -127,7 +128,7 @@ class GradBucketReducer:
         for n, o, k in self.opt.layout:
             if n.startswith("backbone.head") or (trainable is not None and n not in trainable):
                 continue
-            st = stage_of(n, getattr(net, "depth", 12))
+            st = "deferred" if n in self.deferred else stage_of(n, getattr(net, "depth", 12))
             self.ranges.setdefault(st, []).append([o, o + (k + 63) // 64 * 64])
         for st, rs in self.ranges.items():
             self.ranges[st] = self._merge(rs)
@@ -142,6 +143,18 @@ class GradBucketReducer:
             else:
                 merged.append([a, b])
         return merged
+
+    def defer(self, names):
+        """Leave the arena slices of `names` out of every stage hook: they are reduced by `allreduce_grads`, i.e. after whatever the caller
+        does between backward and the exchange.  For gradients that reach the arena only after the model's backward -- the open-vocabulary
+        trainer's queries, whose gradient autograd delivers outside the arena (dasm_trainer.OvDasmTrainer) -- a stage hook would reduce the
+        slice while it still holds zeros.  No engine stage is called "deferred", so those slices are always left to `allreduce_grads`."""
+        names = frozenset(names)
+        if names != self.deferred:
+            if self.fired or self.carry or self.pending:
+                raise RuntimeError("GradBucketReducer.defer() between a backward and its allreduce_grads()")
+            self.deferred = names
+            self._build_ranges()
 
     def _refresh(self):
         """A parameter un-frozen (or frozen) since the ranges were built would otherwise silently drop out of (or stay in) the

@@ -22,6 +22,7 @@ import pandas as pd
 import torch
 
 from . import filter as dev_filter
+from .ops import call
 
 
 class Encoder:
@@ -217,6 +218,117 @@ class WeakF1Macro:
         return float(f1.mean())
 
 
+AP_CHUNK = 20000        # clips per LDS sort of sed_ap_compute (its maximum): the validation split (16 891 clips) is one chunk
+
+
+class MultilabelAveragePrecision:
+    """torchmetrics 0.11 `MultilabelAveragePrecision(num_labels, average, thresholds=None)` as the AudioSet-Strong recipes construct it
+    (passt_cnn/train.py:239-314, detect_any_sound/passt/train.py:134-211, open_vocabulary.py:146-227), on HIP kernels (csrc/metrics.hip).
+
+    `update(preds [B, C], target [B, C])` appends the batch to class-major device storage in one stream-ordered call and never waits for the
+    device.  Like torchmetrics, a batch with any score outside [0, 1] is stored as its sigmoid (decided per batch, on the device).  The
+    target may be integer, bool or a {0, 1}-valued float: the passt_cnn loop hands over a float target (train.py:267); whether 0.11 itself
+    accepts one is not checked here.  Scores are kept as fp32.  `compute()` raises on what torchmetrics' argument validation rejects: no
+    update, a target outside {0, 1}, a NaN score.  `compute_on_step` is accepted and ignored (calling the object updates and returns None).
+    `average`: "macro" (mean over classes with a positive), "weighted" (weights = positives per class), None / "none" ([C]); a class without
+    a positive scores NaN and is left out of both averages with torchmetrics' warning.  "micro" is not implemented."""
+
+    def __init__(self, num_labels, average="macro", compute_on_step=None, chunk=AP_CHUNK, **kwargs):
+        if average == "micro":
+            raise NotImplementedError("MultilabelAveragePrecision: average='micro' is not implemented on the HIP path")
+        if average not in ("macro", "weighted", "none", None):
+            raise ValueError(f"Expected argument `average` to be one of ('macro', 'weighted', 'none', None), but got {average}")
+        for k, v in kwargs.items():
+            if k == "thresholds" and v is None or k == "validate_args" or k == "ignore_index" and v is None:
+                continue
+            raise NotImplementedError(f"MultilabelAveragePrecision: unsupported argument {k}={v!r}")
+        self.num_labels, self.average, self.chunk = int(num_labels), average, int(chunk)
+        self.device = None
+        self.reset()
+
+    def reset(self):
+        self.n = 0
+        self.cap = 0
+        self.scores = self.labels = None
+        self._flag = self._status = None
+
+    def to(self, device):
+        return self         # (storage lives on the device of the first batch)
+
+    def __call__(self, preds, target):
+        self.update(preds, target)
+
+    def _grow(self, need, dev):
+        cap = max(need, 2 * self.cap, 64)
+        C = self.num_labels
+        scores = torch.empty(C, cap, dtype=torch.float32, device=dev)
+        labels = torch.empty(C, cap, dtype=torch.uint8, device=dev)
+        if self.scores is not None:
+            call("sed_ap_grow", self.scores, self.labels, C, self.n, self.cap, scores, labels, cap)
+        self.scores, self.labels, self.cap = scores, labels, cap
+
+    def update(self, preds, target):
+        if preds.dim() != 2 or preds.shape[1] != self.num_labels or tuple(target.shape) != tuple(preds.shape):
+            raise ValueError(f"preds and target must both be [batch, {self.num_labels}], got {tuple(preds.shape)} and {tuple(target.shape)}")
+        if preds.is_floating_point() is False:
+            raise ValueError("Expected argument `preds` to be a floating tensor")
+        dev = preds.device
+        if self.device is not None and dev != self.device:
+            raise ValueError(f"batches on different devices ({self.device}, {dev})")
+        self.device = dev
+        p = preds.detach().to(torch.float32).contiguous()
+        t = target.detach().to(device=dev, dtype=torch.float32).contiguous()
+        B = p.shape[0]
+        if self._status is None:
+            self._flag = torch.zeros(64, dtype=torch.int32, device=dev)     # (sed_ap_append's per-workgroup flag words)
+            self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.n + B > self.cap:
+            self._grow(self.n + B, dev)
+        call("sed_ap_append", p, t, B, self.num_labels, self.n, self.cap, self._flag, self._status, self.scores, self.labels)
+        self.n += B
+
+    def per_class(self):
+        """-> (ap [C] float64, positives [C] int32), device tensors."""
+        if self.n == 0:
+            raise RuntimeError("MultilabelAveragePrecision.compute() called before any update")
+        status = int(self._status.item())
+        if status & 4:
+            raise RuntimeError("Detected the following values in `target`: values outside {0, 1}; expected only 0 and 1")
+        if status & 2:
+            raise RuntimeError("Detected NaN values in `preds`")
+        C, N, ch = self.num_labels, self.n, self.chunk
+        nch = (N + ch - 1) // ch
+        dev = self.device
+        a_sorted = p_sorted = None
+        if nch > 1:
+            a_sorted = torch.empty(C * nch * ch, dtype=torch.int32, device=dev)
+            p_sorted = torch.empty(C * nch * ch, dtype=torch.int32, device=dev)
+        pos_cnt = torch.empty(C * nch, dtype=torch.int32, device=dev)
+        partial = torch.empty(C * nch, dtype=torch.int64, device=dev)
+        ap = torch.empty(C, dtype=torch.float64, device=dev)
+        npos = torch.empty(C, dtype=torch.int32, device=dev)
+        call("sed_ap_compute", self.scores, self.labels, C, N, self.cap, ch, a_sorted, p_sorted, pos_cnt, partial, ap, npos)
+        return ap, npos
+
+    def compute(self):
+        ap, npos = self.per_class()
+        res = ap.float()
+        if self.average in (None, "none"):
+            return res
+        nan = torch.isnan(res)
+        if bool(nan.any()):
+            import warnings
+            warnings.warn(f"Average precision score for one or more classes was `nan`. Ignoring these classes in {self.average}-average",
+                          UserWarning)
+        idx = ~nan
+        if self.average == "macro":
+            return res[idx].mean()
+        w = npos.float()[idx]
+        s = w.sum()
+        w = w / s if float(s) != 0 else torch.zeros_like(w)
+        return (res[idx] * w).sum()
+
+
 ScoreBufferTuple = namedtuple("ScoreBufferTuple", ["raw_student", "raw_teacher", "post_student", "post_teacher"])
 
 
@@ -346,3 +458,145 @@ class Evaluator:
         """train.py:470-478."""
         for name in ScoreBufferTuple._fields:
             write_sed_scores(getattr(self.scores, name), os.path.join(save_folder, name))
+
+
+def mean_psds_per_type(single_psds, type_dict):
+    """passt_cnn/train.py:223-237: mean of the per-class PSDS of each class type ({"common": .., "rare": ..}), for a PSDS computed
+    elsewhere (the PSDS itself needs sed_scores_eval)."""
+    ret = {category: [] for category in set(type_dict.values())}
+    for event, psds in single_psds.items():
+        ret[type_dict[event]].append(psds)
+    return {category: sum(v) / len(v) for category, v in ret.items()}
+
+
+def remove_extra_events(scores_buffer, events):
+    """passt_cnn/train.py:169-172 (`_remove_extra_events`): drops the columns of `events` from every score table, in place."""
+    events = list(events)
+    for audio_id, df in scores_buffer.items():
+        scores_buffer[audio_id] = df.drop(events, axis=1)
+    return scores_buffer
+
+
+class AudiosetStrongEvaluator:
+    """Per-batch body of the AudioSet-Strong validation / test loops:
+      mode "closed"           passt_cnn/train.py:239-314 / 323-370 (PaSST_CNN, 407 classes): mAP of the weak output
+      mode "dasm"             detect_any_sound/passt/train.py:134-211 / 213-269 (DASM, out_type 'sigmoid'): mAP of the tagging output at_out
+      mode "open_vocabulary"  open_vocabulary.py:146-227 / 229-301: DASM queried common classes first with the decoder's attention mask
+                              (get_common_first_query / get_att_mask), every output put back into class order (reorder_pred)
+    Eval-mode forward with `val_kwargs` (`test_kwargs` when test=True), mAP through `MultilabelAveragePrecision` on
+    labels_weak = labels.sum(-1) >= 1, score tables of the post-processed posteriors with the device median filter (no weak mask).  A
+    batch's tables are built on the host while the GPU runs the next batch's forward (`_HostStage`, like `Evaluator`); `scores` waits for
+    whatever is pending.
+
+    Median window: the reference computes `int(median_window / 156 * pred_len)`, ONE int, and hands it to batched_decode_preds, which
+    needs a per-class list -- its validation fails with a nonzero window.  Here the int is expanded to [w] * C.
+    `events_set`: the classes of the ground truth; the other columns are dropped from the post-processed tables (`psds` does that before
+    computing, train.py:174-175).  The 'logit' tagging output of DASM is out of scope, as in dasm_trainer."""
+
+    MODES = ("closed", "dasm", "open_vocabulary")
+
+    def __init__(self, net, encoder, config, mode, type_dict=None, events_set=None, test=False):
+        if mode not in self.MODES:
+            raise ValueError(f"mode must be one of {self.MODES}")
+        self.net, self.encoder, self.config, self.mode, self.test = net, encoder, config, mode, test
+        name = net.get_model_name()
+        if mode != "closed":
+            out_type = config[name].get("init_kwargs", {}).get("at_param", {}).get("out_type", "sigmoid")
+            if out_type != "sigmoid":
+                raise NotImplementedError("AudiosetStrongEvaluator: the 'logit' tagging output is out of scope on the HIP path")
+        self.kwargs = config[name]["test_kwargs" if test else "val_kwargs"]
+        tr = config["training"]
+        w = int(tr["median_window"] / 156 * config["feature"]["pred_len"])                 # train.py:156-160
+        self.median_filter = [w] * len(encoder.labels) if w else None
+        self.filter_type = tr.get("filter_type", "median") if test else "median"
+        self.events_set = events_set
+        self.type_dict = None
+        self.mask = None
+        if mode == "open_vocabulary":
+            from .dasm_trainer import common_type_mask, load_type_dict
+            self.type_dict = load_type_dict(type_dict if type_dict is not None else config["dataset"]["event_state"])
+            self.mask = common_type_mask(encoder.labels, self.type_dict, next(net.parameters()).device)
+            # the common-first permutation, its inverse and the attention mask, once: per batch only index_select runs (the reference's
+            # boolean-mask forms, dasm_trainer.get_common_first_query / reorder_pred, wait for the device on every call)
+            from .dasm_trainer import get_att_mask
+            self._first = torch.cat([torch.nonzero(self.mask).reshape(-1), torch.nonzero(~self.mask).reshape(-1)])
+            self._inv = torch.argsort(self._first)
+            self._att = get_att_mask(self.mask)
+        elif type_dict is not None:
+            from .dasm_trainer import load_type_dict
+            self.type_dict = load_type_dict(type_dict)
+        self.map = MultilabelAveragePrecision(len(encoder.labels), average="macro", compute_on_step=False)
+        self._post, self._raw = {}, {}
+        self._stage = [_HostStage(), _HostStage()]
+        self._n = 0
+        self._pending = None
+
+    def forward(self, feat, pad_mask):
+        """-> strong [B, C, T], weak [B, C], at_out [B, C] (None for the closed set) in the encoder's class order."""
+        if self.mode == "open_vocabulary":
+            q = self.net.at_query
+            q = ([t.detach().index_select(0, self._first) for t in q] if isinstance(q, (list, tuple, torch.nn.ParameterList))
+                 else q.detach().index_select(0, self._first))                              # get_common_first_query
+            strong, weak, other = self.net(feat, pad_mask=pad_mask, query=q, tgt_mask=self._att, **self.kwargs)
+            back = lambda x: x.index_select(1, self._inv)                                    # reorder_pred
+            return back(strong), back(weak), back(other["at_out"])
+        strong, weak, other = self.net(feat, pad_mask=pad_mask, **self.kwargs)
+        return strong, weak, other.get("at_out")
+
+    def _enqueue(self, strong, paths):
+        if strong.shape[0] > len(paths):
+            raise IndexError("list index out of range")     # (batched_decode_preds' contract)
+        n = strong.shape[0]
+        st = self._stage[self._n % 2]
+        self._n += 1
+        raw, post = _scores_device(strong, n, self.median_filter, self.filter_type, None, False)
+        job = {"paths": list(paths), "frames": strong.shape[-1], "stage": st, "raw": st.put("raw", raw),
+               "post": st.put("post", post) if post is not None else None}
+        st.mark()
+        return job
+
+    def _finish(self, job):
+        if job is None:
+            return
+        job["stage"].wait()
+        raw, post = _scores_tables(job["raw"].numpy(), job["post"].numpy() if job["post"] is not None else None, job["paths"],
+                                   self.encoder, None, job["frames"])
+        if self.events_set is not None:
+            extra = set(self.encoder.labels) - set(self.events_set)
+            post = remove_extra_events(post, extra)
+        self._raw.update(raw)
+        self._post.update(post)
+
+    def flush(self):
+        job, self._pending = self._pending, None
+        self._finish(job)
+
+    @property
+    def scores(self):
+        """audio_id -> post-processed score DataFrame of every batch so far."""
+        self.flush()
+        return self._post
+
+    @property
+    def raw_scores(self):
+        self.flush()
+        return self._raw
+
+    def compute_map(self):
+        return self.map.compute()
+
+    def mean_psds_per_type(self, single_psds):
+        return mean_psds_per_type(single_psds, self.type_dict)
+
+    @torch.no_grad()
+    def step(self, wav, labels, pad_mask, paths):
+        self.net.eval()
+        ext = self.net.get_feature_extractor()
+        ext.eval()
+        feat = ext.logmel(wav)                                        # preprocess_eval (passt_cnn/train.py:150-153)
+        strong, weak, at_out = self.forward(feat, pad_mask)
+        self.map.update(weak if self.mode == "closed" else at_out, labels.sum(-1) >= 1)
+        job = self._enqueue(strong, paths)
+        self._finish(self._pending)                                   # the previous batch's tables, under this batch's filters
+        self._pending = job
+        return strong, weak, at_out
