@@ -250,6 +250,21 @@ int sed_relpos_attn_bwd(const void* Qu, const void* Qut, const void* Qv, const v
 /* (dSt, Pst: [B H, Tpad, Tpad] bf16 scratch slabs, ZERO outside the region the kernels write -- rows = keys, columns = queries.  The dQ
  *  kernel stores dS^T there for the positional-table gradient and, when Pst is given, P^T as well: dK and dV are then two contractions
  *  over the stored slabs (a streaming kernel) instead of a second recomputation of the scores; Pst = NULL keeps the recomputing kernel.) */
+/* Local-window forms (PaSST_SED(decoder_win_len=...): src/models/transformer/mask.py:7-23 diagonal_mask, applied per head by
+ * src/models/transformer_decoder.py:96-119).  half_width: device int32 [H], hw[h] = window_len[h] / 2 (>= 1).  Query i of head h sees key j
+ * iff max(0, i - hw) <= j < min(T, i + hw): hw keys to the left, the key itself, hw - 1 to the right -- the right edge is exclusive.
+ * Masked scores are -inf before the softmax: their probability and gradient are exact zeros; LSE is the log-sum-exp over the allowed
+ * keys.  hw >= T is the full window.  Every other argument, layout and result is that of the unbanded entry point; key (query) tiles
+ * that no query (key) of a workgroup can see are skipped.  Slabs: the dQ kernel writes every slab tile it visits in full (zeros out of
+ * band) and the other kernels read only those tiles, so tiles outside the band may hold anything (e.g. an earlier full-window call). */
+int sed_relpos_attn_band_fwd(const void* Qu, const void* Qv, const void* K, const void* Vt, const void* P, void* O, void* O_split,
+                             float* LSE, int B, int H, int T, int Tpad, int Rpad, int f16, int o_f32,
+                             const int32_t* half_width /* device, [H] */, hipStream_t stream);
+int sed_relpos_attn_band_bwd(const void* Qu, const void* Qut, const void* Qv, const void* Qvt, const void* K, const void* Kt,
+                             const void* V, const void* P, const void* Pt, const void* O, const void* dO, const float* LSE,
+                             float* Dtmp, void* dOh, void* dOt, void* dqkv, void* dSt, void* Pst, float* dP, float* du, float* dv, int B,
+                             int H, int T, int Tpad, int Rpad, int need_param_grads, int f16, int o_kind,
+                             const int32_t* half_width /* device, [H] */, hipStream_t stream);
 
 /* ------------------------------------------------------------------ norms / glue / heads / optimiser */
 /* nn.LayerNorm over D=768 (passt.py:361-362,580; passt_sed.py:128; timm Block norms); y = LN(in_scale*x).

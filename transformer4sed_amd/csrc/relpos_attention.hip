@@ -20,6 +20,18 @@
 
 #define BAND_ROWS 192
 
+// BAND: the key tiles the dQ workgroup of the 128 queries from I0 visits, [lo, hi] -- those that meet [I0 - hw, I0 + 127 + hw) inside
+// [0, T).  The slab invariant rests on this one function: the dQ kernel stores every (128-query x 64-key) slab tile it visits in full,
+// with exact zeros at the out-of-band pairs, and the stream and dP kernels of the same call read a slab tile only where this range
+// says the dQ kernel visited it.  Tiles outside the range are neither written nor read: a slab that still holds the full-window
+// content of an earlier call there (the engine's pool) is harmless.
+__device__ __forceinline__ int band_hw(const int* __restrict__ HW, int h) { return min(max(__builtin_amdgcn_readfirstlane(HW[h]), 1), 1 << 24); }
+__device__ __forceinline__ int band_tile_lo(int I0, int hw) { return max(I0 - hw, 0) >> 6; }
+__device__ __forceinline__ int band_tile_hi(int I0, int hw, int T) { return min(I0 + 126 + hw, T - 1) >> 6; }
+
+// A head whose window covers the whole sequence (hw >= T) runs the unbanded body: every band kernel picks, per workgroup and uniformly,
+// between the two instantiations of its body, so such a head costs what the unbanded entry point costs.
+
 struct BandRegs { uint4 x0, x1, x2, x3, x4, x5; };
 
 __device__ __forceinline__ uint4 band_load1(const bf16_t* Ph, int row, int R, int c) {
@@ -103,11 +115,17 @@ typedef __attribute__((address_space(3))) void* rp_lds_ptr_t;
 // NW waves (16 NW queries) per workgroup; the ring holds the 16 NW + 63 band rows a tile touches plus the 64 the next one adds
 #define FW16_RING(NW) (16 * (NW) + 128)
 #define FW16_LDS(NW) (16384 + FW16_RING(NW) * 128 + (NW) * FW16_WL)
-template <bool F16, bool O32, int NW>
-__global__ __launch_bounds__(64 * NW) void relpos_fwd_kernel(const bf16_t* __restrict__ Qu, const bf16_t* __restrict__ Qv,
+// BAND (local-window attention, decoder_win_len): query i sees key j iff -hw <= j - i < hw with hw = half_width[h] (mask.py:7-23:
+// hw keys to the left, the key itself, hw - 1 to the right).  The workgroup walks only the key tiles t_lo .. t_hi that meet the band
+// of one of its queries -- a uniform function of the block index and the head's hw; band indices n stay relative to tile 0, so the
+// ring and its prologue simply start at n = 64 t_lo.  A wave skips the arithmetic of a tile that lies outside the band of all of its
+// 16 queries; inside an edge tile the out-of-band scores get the -1e30f sentinel of the keys >= T before the running maximum is taken.
+template <bool F16, bool O32, int NW, bool BAND>
+__device__ __forceinline__ void relpos_fwd_body(const bf16_t* __restrict__ Qu, const bf16_t* __restrict__ Qv,
                                                          const bf16_t* __restrict__ K, const bf16_t* __restrict__ Vt,
                                                          const bf16_t* __restrict__ P, bf16_t* __restrict__ O,
-                                                         bf16_t* __restrict__ Osplit, float* __restrict__ LSE, int T, int Tpad, int H, int Rpad) {
+                                                         bf16_t* __restrict__ Osplit, float* __restrict__ LSE, int T, int Tpad, int H, int Rpad,
+                                                         const int hwv) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds_fw[];
     unsigned char* lds_k = lds_fw;                      // K rows of the tile (permuted, see above)
     unsigned char* lds_vt = lds_fw + 8192;              // V^T tile [64 d][64 keys]
@@ -130,7 +148,12 @@ __global__ __launch_bounds__(64 * NW) void relpos_fwd_kernel(const bf16_t* __res
         const int vo = (RB0 + n0 + prow) * (HD * 2) + ((pch ^ ((slot >> 1) & 7)) << 4);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rp, (rp_lds_ptr_t)(lds_band + s0 * 128), 16, vo, 0, 0, 0);
     };
-    for (int n0 = 8 * wave; n0 < 16 * NW + 64; n0 += 8 * NW) dma_band(n0);      // rows tile 0 touches
+    const int ntiles = (T + KVB - 1) / KVB;
+    // key tiles of the walk (BAND: those that meet [I0 - hw, I0 + 16 NW - 1 + hw) inside [0, T); hw is clamped so that no sum overflows)
+    const int hw = hwv;
+    const int t_lo = BAND ? max(I0 - hw, 0) >> 6 : 0;
+    const int t_hi = BAND ? min(I0 + 16 * NW - 2 + hw, T - 1) >> 6 : ntiles - 1;
+    for (int n0 = 8 * wave; n0 < 16 * NW + 64; n0 += 8 * NW) dma_band(64 * t_lo + n0);      // rows the first tile touches
     const int trow = (tid >> 3) & 63, tch = tid & 7;   // this thread's 16-byte chunk of a [64][64] tile (threads 0..511)
     const bool loader = tid < 512;
     uint4 pk = make_uint4(0, 0, 0, 0), pvt = make_uint4(0, 0, 0, 0);
@@ -143,7 +166,7 @@ __global__ __launch_bounds__(64 * NW) void relpos_fwd_kernel(const bf16_t* __res
         pvt = *reinterpret_cast<const uint4*>(Vt + hbt + (size_t)trow * Tpad + j0 + tch * 8);
     };
     const int krow_lds = (trow & 32) + (((trow >> 2) & 1) << 4) + (((trow >> 3) & 3) << 2) + (trow & 3);
-    gload(0);
+    gload(t_lo);
     int qrow = q0 + c;
     const bool qvalid = qrow < T;
     qrow = qvalid ? qrow : T - 1;
@@ -164,16 +187,20 @@ __global__ __launch_bounds__(64 * NW) void relpos_fwd_kernel(const bf16_t* __res
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("" ::"v"(quf[0]), "v"(quf[1]), "v"(qvf[0]), "v"(qvf[1]));   // (arrived: no compiler wait inside the loop)
     __syncthreads();
-    const int ntiles = (T + KVB - 1) / KVB;
     const int swc = (c >> 1) & 7;
-    for (int t = 0; t < ntiles; ++t) {
+    for (int t = t_lo; t <= t_hi; ++t) {
         const int j0 = t * KVB;
-        const bool more = t + 1 < ntiles;
+        const bool more = t < t_hi;
         if (more) {   // tile t + 1: the 64 band rows it adds replace the slots tile t - 1 retired (one piece per wave 0..7)
             if (wave < 8) dma_band(64 * t + 16 * NW + 64 + 8 * wave);
             gload(t + 1);
         }
+        // BAND: does the tile meet the band of one of this wave's queries (wave-uniform), and does it reach past the band of one?
+        const bool wact = !BAND || (j0 + KVB - 1 >= q0 - hw && j0 < q0 + 15 + hw);
+        const bool wedge = BAND && !(j0 >= q0 + 15 - hw && j0 + KVB - 1 < q0 + hw);
         const int nb = 64 * t + 16 * (NW - 1 - wave);    // this wave's band base
+        f32x4_t st[4];
+        if (wact) {
         // ---- G^T[rho, q] = P_band[rho, :] . Qv[q, :]  (5 blocks of 16 rho) -> wave-private LDS
 #pragma unroll
         for (int blk = 0; blk < 5; ++blk) {
@@ -188,7 +215,6 @@ __global__ __launch_bounds__(64 * NW) void relpos_fwd_kernel(const bf16_t* __res
             for (int r = 0; r < 4; ++r) gs[85 * c + 1 + 16 * blk + 4 * g + r] = gacc[r];
         }
         // ---- S^T = K Qu^T + skew(G^T): block kb, register r <-> key jj = 32 (kb >> 1) + 4 (kb & 1) + 8 g + r
-        f32x4_t st[4];
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) st[kb] = *reinterpret_cast<const f32x4_t*>(gs + 84 * c + 16 + 32 * (kb >> 1) + 4 * (kb & 1) + 8 * g);
 #pragma unroll
@@ -198,13 +224,24 @@ __global__ __launch_bounds__(64 * NW) void relpos_fwd_kernel(const bf16_t* __res
             for (int ks = 0; ks < 2; ++ks)
                 st[kb] = mfma16x<F16>(*reinterpret_cast<const s16x8_t*>(kp + (((4 * ks + g) ^ swc) << 4)), quf[ks], st[kb]);
         }
+        }
         // barrier A: every wave has read the K rows of tile t -> the prefetched K rows go to LDS
         if (more) {
             __syncthreads();
             if (loader) *reinterpret_cast<uint4*>(lds_k + k_off(krow_lds, tch)) = pk;
         }
+        if (wact) {
         // ---- online softmax of the lane's query over its 16 keys, combined over the four lane groups
-        if (j0 + KVB > T) {   // keys >= T exist only in the last tile
+        if (wedge) {          // out-of-band keys of an edge tile (and keys >= T): the sentinel, before the running maximum
+            const int dq = j0 + 8 * g - (q0 + c);
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int jj = 32 * (kb >> 1) + 4 * (kb & 1) + r;
+                    st[kb][r] = (dq + jj >= -hw && dq + jj < hw && j0 + 8 * g + jj < T) ? st[kb][r] : -1e30f;
+                }
+        } else if (j0 + KVB > T) {   // keys >= T exist only in the last tile
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
@@ -228,7 +265,10 @@ __global__ __launch_bounds__(64 * NW) void relpos_fwd_kernel(const bf16_t* __res
         for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(st[kb][r], SCALE_LOG2E, -m_new));
+                float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(st[kb][r], SCALE_LOG2E, -m_new));
+                // (a query may see no key of an edge tile it meets before its own band: m_new is then the rounded sentinel itself and
+                //  the exponent above only rounding residue -- the masked pairs are exact zeros whatever it is)
+                if (wedge) pv = st[kb][r] <= -1e29f ? 0.f : pv;
                 st[kb][r] = pv;
                 psum += pv;
             }
@@ -250,6 +290,7 @@ __global__ __launch_bounds__(64 * NW) void relpos_fwd_kernel(const bf16_t* __res
                 o[db] = mfma16x<F16>(*reinterpret_cast<const s16x8_t*>(rowp + (((4 * ks + g) ^ swc) << 4)), pf, o[db]);
             }
         }
+        }
         // barrier B: every wave has read V^T of tile t and this wave's band piece of tile t + 1 has landed
         if (more) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -258,6 +299,7 @@ __global__ __launch_bounds__(64 * NW) void relpos_fwd_kernel(const bf16_t* __res
         }
     }
     if (qvalid) {
+        // (BAND: a query always sees at least its own key, so l_run > 0 as in the full window)
         const float inv = 1.0f / l_run;
         const int q = q0 + c;
         if (O32) {
@@ -294,24 +336,39 @@ __global__ __launch_bounds__(64 * NW) void relpos_fwd_kernel(const bf16_t* __res
     }
 }
 
-template <bool F16, bool O32, int NW>
-static void launch_relpos_fwd(const void* Qu, const void* Qv, const void* K, const void* Vt, const void* P, void* O, void* Os, float* LSE, int B,
-                              int H, int T, int Tpad, int Rpad, hipStream_t stream) {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)relpos_fwd_kernel<F16, O32, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, FW16_LDS(NW)); attr = true; }
-    hipLaunchKernelGGL((relpos_fwd_kernel<F16, O32, NW>), dim3(cdiv(T, 16 * NW), B * H), dim3(64 * NW), FW16_LDS(NW), stream, (const bf16_t*)Qu,
-                       (const bf16_t*)Qv, (const bf16_t*)K, (const bf16_t*)Vt, (const bf16_t*)P, (bf16_t*)O, (bf16_t*)Os, LSE, T, Tpad, H, Rpad);
+template <bool F16, bool O32, int NW, bool BAND>
+__global__ __launch_bounds__(64 * NW) void relpos_fwd_kernel(const bf16_t* __restrict__ Qu, const bf16_t* __restrict__ Qv,
+                                                         const bf16_t* __restrict__ K, const bf16_t* __restrict__ Vt,
+                                                         const bf16_t* __restrict__ P, bf16_t* __restrict__ O,
+                                                         bf16_t* __restrict__ Osplit, float* __restrict__ LSE, int T, int Tpad, int H, int Rpad,
+                                                         const int* __restrict__ HW) {
+    if (BAND) {
+        const int hw = band_hw(HW, blockIdx.y % H);
+        if (hw < T) { relpos_fwd_body<F16, O32, NW, true>(Qu, Qv, K, Vt, P, O, Osplit, LSE, T, Tpad, H, Rpad, hw); return; }
+    }
+    relpos_fwd_body<F16, O32, NW, false>(Qu, Qv, K, Vt, P, O, Osplit, LSE, T, Tpad, H, Rpad, 0);
 }
-extern "C" int sed_relpos_attn_fwd(const void* Qu, const void* Qv, const void* K, const void* Vt, const void* P,
-                                   void* O, void* O_split, float* LSE, int B, int H, int T, int Tpad, int Rpad, int f16, int o_f32,
-                                   hipStream_t stream) {
+
+template <bool F16, bool O32, int NW, bool BAND>
+static void launch_relpos_fwd(const void* Qu, const void* Qv, const void* K, const void* Vt, const void* P, void* O, void* Os, float* LSE, int B,
+                              int H, int T, int Tpad, int Rpad, const int* hw, hipStream_t stream) {
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)relpos_fwd_kernel<F16, O32, NW, BAND>, hipFuncAttributeMaxDynamicSharedMemorySize, FW16_LDS(NW)); attr = true; }
+    hipLaunchKernelGGL((relpos_fwd_kernel<F16, O32, NW, BAND>), dim3(cdiv(T, 16 * NW), B * H), dim3(64 * NW), FW16_LDS(NW), stream, (const bf16_t*)Qu,
+                       (const bf16_t*)Qv, (const bf16_t*)K, (const bf16_t*)Vt, (const bf16_t*)P, (bf16_t*)O, (bf16_t*)Os, LSE, T, Tpad, H, Rpad, hw);
+}
+template <bool BAND>
+static int relpos_attn_fwd(const void* Qu, const void* Qv, const void* K, const void* Vt, const void* P,
+                           void* O, void* O_split, float* LSE, int B, int H, int T, int Tpad, int Rpad, int f16, int o_f32,
+                           const int* hw, hipStream_t stream) {
     (void)hipGetLastError();
     if (T <= 0 || (T % 8) || Tpad % 64 || Tpad < T || Rpad % 64 || Rpad < 2 * T - 1 || (O_split != nullptr && !o_f32)) return SED_ERR_ARG;
+    if (BAND && hw == nullptr) return SED_ERR_ARG;
     // 16 waves (256 queries) per workgroup when the sequence is long enough to fill them: four waves per SIMD, K / V^T tiles staged once per
     // 256 queries (the 8-wave form serves short sequences)
     const bool big = T > 128;
-#define SED_RP_FWD(F, O32) { if (big) launch_relpos_fwd<F, O32, 16>(Qu, Qv, K, Vt, P, O, O_split, LSE, B, H, T, Tpad, Rpad, stream); \
-                             else launch_relpos_fwd<F, O32, 8>(Qu, Qv, K, Vt, P, O, O_split, LSE, B, H, T, Tpad, Rpad, stream); }
+#define SED_RP_FWD(F, O32) { if (big) launch_relpos_fwd<F, O32, 16, BAND>(Qu, Qv, K, Vt, P, O, O_split, LSE, B, H, T, Tpad, Rpad, hw, stream); \
+                             else launch_relpos_fwd<F, O32, 8, BAND>(Qu, Qv, K, Vt, P, O, O_split, LSE, B, H, T, Tpad, Rpad, hw, stream); }
     if (f16 && o_f32) SED_RP_FWD(true, true)
     else if (f16) SED_RP_FWD(true, false)
     else if (o_f32) SED_RP_FWD(false, true)
@@ -319,10 +376,23 @@ extern "C" int sed_relpos_attn_fwd(const void* Qu, const void* Qv, const void* K
 #undef SED_RP_FWD
     return sed_check_launch();
 }
+extern "C" int sed_relpos_attn_fwd(const void* Qu, const void* Qv, const void* K, const void* Vt, const void* P,
+                                   void* O, void* O_split, float* LSE, int B, int H, int T, int Tpad, int Rpad, int f16, int o_f32,
+                                   hipStream_t stream) {
+    return relpos_attn_fwd<false>(Qu, Qv, K, Vt, P, O, O_split, LSE, B, H, T, Tpad, Rpad, f16, o_f32, nullptr, stream);
+}
+extern "C" int sed_relpos_attn_band_fwd(const void* Qu, const void* Qv, const void* K, const void* Vt, const void* P,
+                                        void* O, void* O_split, float* LSE, int B, int H, int T, int Tpad, int Rpad, int f16, int o_f32,
+                                        const int32_t* half_width, hipStream_t stream) {
+    return relpos_attn_fwd<true>(Qu, Qv, K, Vt, P, O, O_split, LSE, B, H, T, Tpad, Rpad, f16, o_f32, half_width, stream);
+}
 
 // ---------------------------------------------------------------------------------------------------
 // backward kernel 1: dK, dV   (workgroup = 128 keys; loops over 64-query tiles; lane owns a key column)
 // ---------------------------------------------------------------------------------------------------
+// BAND: key j is seen by the queries j - hw < i <= j + hw; the workgroup walks the query tiles that meet those of its 128 keys and
+// zeroes P (hence dS) of the out-of-band pairs inside them.  (This kernel sits at the 256-VGPR limit and its register allocation moves
+// with any restructuring: the unbanded kernel and the band kernel's two bodies are siblings that include one body text, relpos_dkdv_body.h.)
 template <bool SF16>
 __global__ __launch_bounds__(256) void relpos_bwd_dkdv_kernel(
     const bf16_t* __restrict__ Qu, const bf16_t* __restrict__ Qut, const bf16_t* __restrict__ Qv,
@@ -333,128 +403,36 @@ __global__ __launch_bounds__(256) void relpos_bwd_dkdv_kernel(
     __shared__ __attribute__((aligned(16))) unsigned char lds_band[BAND_ROWS * 128];
     __shared__ __attribute__((aligned(16))) float lds_g[4][32 * 65];
     __shared__ __attribute__((aligned(16))) float lstat[2][64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lg = lane >> 5;
-    const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
-    const int J0 = blockIdx.x * 128, key0 = J0 + wave * 32;
-    const int R = 2 * T - 1;
-    const size_t hb = (size_t)bh * T * HD, hbt = (size_t)bh * HD * Tpad;
-    const bf16_t* Ph = P + (size_t)h * Rpad * HD;
-    int krow = key0 + lr;
-    const bool key_valid_lane = krow < T;
-    krow = krow < T ? krow : T - 1;
-    s16x8_t kf[4], vf[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        kf[s] = *reinterpret_cast<const s16x8_t*>(K + hb + (size_t)krow * HD + 16 * s + 8 * lg);
-        vf[s] = *reinterpret_cast<const s16x8_t*>(V + hb + (size_t)krow * HD + 16 * s + 8 * lg);
-    }
-    f32x16_t dk[2], dv[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { dk[i][r] = 0.f; dv[i][r] = 0.f; }
-    float* gs = lds_g[wave];
-    const int ntiles = (T + 63) / 64;
-    // next tile's operands travel HBM -> registers while the current tile is being consumed, registers -> LDS afterwards
-    TileRegs r0, r1, r2, r3, r4;
-    BandRegs rb;
-    float rstat = 0.f;
-    auto gload = [&](int t) {
-        const int i0 = t * 64;
-        tile_gload(r0, Qu + hb, i0, T, HD, 0, tid);
-        tile_gload(r1, Qv + hb, i0, T, HD, 0, tid);
-        tile_gload(r2, dOh + hb, i0, T, HD, 0, tid);
-        tile_gload(r3, Qut + hbt, 0, HD, Tpad, i0, tid);
-        tile_gload(r4, dOt + hbt, 0, HD, Tpad, i0, tid);
-        band_gload(rb, Ph, J0 - (i0 + 63) + T - 1, R, tid);
-        if (tid < 128) {
-            const int qi = i0 + (tid & 63);
-            const float* src = (tid < 64) ? LSE : Dv;
-            rstat = qi < T ? src[(size_t)bh * T + qi] : (tid < 64 ? 1e30f : 0.f);  // L2 = +big -> P = 0 for padded queries
-        }
-    };
-    auto lstore = [&]() {
-        tile_lstore_rows(r0, lds[0], tid);
-        tile_lstore_rows(r1, lds[1], tid);
-        tile_lstore_rows(r2, lds[2], tid);
-        tile_lstore_cols(r3, lds[3], tid);
-        tile_lstore_cols(r4, lds[4], tid);
-        band_lstore(rb, lds_band, tid);
-        if (tid < 128) lstat[tid >> 6][tid & 63] = rstat;
-    };
-    gload(0);
-    lstore();
-    __syncthreads();
-    for (int t = 0; t < ntiles; ++t) {
-        if (t + 1 < ntiles) gload(t + 1);
-#pragma unroll
-        for (int qb = 0; qb < 2; ++qb) {
-            const int rowoff = 32 * (wave - qb + 1);
-            // band product G[i, rho] (rows = queries, column = rho): A = Qv rows, B = band rows
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk) {
-                f32x16_t g;
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    g = mfma32t<SF16>(lds_frag_rows(lds[1], 32 * qb + lr, 2 * s + lg),
-                                      lds_frag_rows(lds_band, rowoff + 32 * blk + lr, 2 * s + lg), s == 0 ? zero16 : g);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) gs[mfma32_row(r, lg) * 65 + 32 * blk + lr] = g[r];
-            }
-            f32x16_t s_, dp;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                s_ = mfma32t<SF16>(lds_frag_rows(lds[0], 32 * qb + lr, 2 * s + lg), kf[s], s == 0 ? zero16 : s_);
-                dp = mfma32(lds_frag_rows(lds[2], 32 * qb + lr, 2 * s + lg), vf[s], s == 0 ? zero16 : dp);
-            }
-            __syncthreads();
-            // (a lane whose key is >= T needs no masking: its columns only feed dK / dV rows that are never stored)
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const int qq = 32 * qb + 8 * qd + 4 * lg;
-                const f32x4_t l2 = *reinterpret_cast<const f32x4_t*>(&lstat[0][qq]);
-                const f32x4_t dd = *reinterpret_cast<const f32x4_t*>(&lstat[1][qq]);
-#pragma unroll
-                for (int j = 0; j < 4; j += 2) {
-                    const int r = 4 * qd + j, ii = mfma32_row(r, lg);
-                    const f32x2_t bd = {gs[ii * 65 + lr - ii + 31], gs[(ii + 1) * 65 + lr - ii + 30]};
-                    const f32x2_t c2 = {SCALE_LOG2E, SCALE_LOG2E}, nl = {-l2[j], -l2[j + 1]}, nd = {-dd[j], -dd[j + 1]};
-                    f32x2_t x = {s_[r], s_[r + 1]}, d2 = {dp[r], dp[r + 1]};
-                    x = __builtin_elementwise_fma(x + bd, c2, nl);
-                    const f32x2_t pv = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
-                    d2 = pv * (d2 + nd);
-                    s_[r] = pv.x; s_[r + 1] = pv.y;
-                    dp[r] = d2.x; dp[r + 1] = d2.y;
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const s16x8_t pf = pack_frag(s_, s), dsf = pack_frag(dp, s);
-#pragma unroll
-                for (int db = 0; db < 2; ++db) {
-                    dv[db] = mfma32(pf, lds_frag_cols(lds[4], 32 * db + lr, 8 * qb + 4 * s + lg), dv[db]);
-                    dk[db] = mfma32(dsf, lds_frag_cols(lds[3], 32 * db + lr, 8 * qb + 4 * s + lg), dk[db]);
-                }
-            }
-            __syncthreads();
-        }
-        if (t + 1 < ntiles) {
-            lstore();
-            __syncthreads();
-        }
-    }
-    const int ldq = 3 * H * HD;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int key = key0 + mfma32_row(r, lg);
-            if (key < T) {
-                bf16_t* row = dqkv + ((size_t)b * T + key) * ldq + h * HD + 32 * db + lr;
-                row[H * HD] = f2bf(dk[db][r] * SCALE);
-                row[2 * H * HD] = f2bf(dv[db][r]);
-            }
-        }
+    constexpr bool BAND = false;
+    constexpr int hw = 0;
+#include "relpos_dkdv_body.h"
+}
+// (workgroup memory of the band kernel at file scope: its two bodies share one copy)
+__shared__ __attribute__((aligned(16))) unsigned char dkdvb_lds[5][KVB * 128];
+__shared__ __attribute__((aligned(16))) unsigned char dkdvb_lds_band[BAND_ROWS * 128];
+__shared__ __attribute__((aligned(16))) float dkdvb_lds_g[4][32 * 65];
+__shared__ __attribute__((aligned(16))) float dkdvb_lstat[2][64];
+template <bool SF16, bool BAND>
+__device__ __forceinline__ void relpos_bwd_dkdv_band_body(
+    const bf16_t* __restrict__ Qu, const bf16_t* __restrict__ Qut, const bf16_t* __restrict__ Qv,
+    const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, const bf16_t* __restrict__ P,
+    const bf16_t* __restrict__ dOh, const bf16_t* __restrict__ dOt, const float* __restrict__ LSE,
+    const float* __restrict__ Dv, bf16_t* __restrict__ dqkv, int T, int Tpad, int H, int Rpad, const int hw) {
+    auto& lds = dkdvb_lds;
+    auto& lds_band = dkdvb_lds_band;
+    auto& lds_g = dkdvb_lds_g;
+    auto& lstat = dkdvb_lstat;
+#include "relpos_dkdv_body.h"
+}
+template <bool SF16>
+__global__ __launch_bounds__(256) void relpos_bwd_dkdv_band_kernel(
+    const bf16_t* __restrict__ Qu, const bf16_t* __restrict__ Qut, const bf16_t* __restrict__ Qv,
+    const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, const bf16_t* __restrict__ P,
+    const bf16_t* __restrict__ dOh, const bf16_t* __restrict__ dOt, const float* __restrict__ LSE,
+    const float* __restrict__ Dv, bf16_t* __restrict__ dqkv, int T, int Tpad, int H, int Rpad, const int* __restrict__ HW) {
+    const int hw = band_hw(HW, blockIdx.y % H);
+    if (hw < T) relpos_bwd_dkdv_band_body<SF16, true>(Qu, Qut, Qv, K, V, P, dOh, dOt, LSE, Dv, dqkv, T, Tpad, H, Rpad, hw);
+    else relpos_bwd_dkdv_band_body<SF16, false>(Qu, Qut, Qv, K, V, P, dOh, dOt, LSE, Dv, dqkv, T, Tpad, H, Rpad, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -476,13 +454,13 @@ __global__ __launch_bounds__(256) void relpos_bwd_dkdv_kernel(
 
 #define DQ16_WL 8576                      // per-wave LDS: G [16 q][85] fp32 (5440 B) + dG^T [16 q][96 rho] bf16 (3072 B)
 #define DQ16_LDS (24576 + 65536 + 8 * DQ16_WL)
-template <bool SF16>
-__global__ __launch_bounds__(512) void relpos_bwd_dq_kernel(
+template <bool SF16, bool BAND>
+__device__ __forceinline__ void relpos_bwd_dq_body(
     const bf16_t* __restrict__ Qu, const bf16_t* __restrict__ Qv, const bf16_t* __restrict__ K,
     const bf16_t* __restrict__ Kt, const bf16_t* __restrict__ V, const bf16_t* __restrict__ P,
     const bf16_t* __restrict__ Pt, const bf16_t* __restrict__ dOh, const float* __restrict__ LSE,
     const float* __restrict__ Dv, bf16_t* __restrict__ dqkv, bf16_t* __restrict__ dSt, bf16_t* __restrict__ Pst, float* __restrict__ du,
-    float* __restrict__ dvb, int T, int Tpad, int H, int Rpad) {
+    float* __restrict__ dvb, int T, int Tpad, int H, int Rpad, const int hwv) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds_dq[];
     unsigned char (*lds_kv)[KVB * 128] = reinterpret_cast<unsigned char (*)[KVB * 128]>(lds_dq);                    // K rows, V rows, K^T rows (d)
     unsigned char* lds_band = lds_dq + 3 * KVB * 128;                                                               // ring of P rows, slot = n & 255
@@ -514,11 +492,15 @@ __global__ __launch_bounds__(512) void relpos_bwd_dq_kernel(
         const int vo = (d * Rpad + RB0 + n0) * 2 + ((pch ^ ((d >> 1) & 7)) << 4);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rpt, (rp_lds_ptr_t)(lds_bandT[(n0 >> 6) & 3] + 8 * wave * 128), 16, vo, 0, 0, 0);
     };
-    // ---- prologue: the whole ring (256 rows / 4 panels), tile 0 of K / V / K^T, query-side fragments
+    const int ntiles = (T + KVB - 1) / KVB;
+    const int hw = hwv;
+    const int t_lo = BAND ? band_tile_lo(I0, hw) : 0, t_hi = BAND ? band_tile_hi(I0, hw, T) : ntiles - 1;
+    // ---- prologue: the whole ring (256 rows / 4 panels), the first tile of K / V / K^T, query-side fragments
+    // (band indices n are relative to key tile 0 whatever the first visited tile is: ring slots and panels follow n)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        dma_band(64 * i + 8 * wave);
-        dma_bandT(64 * i);
+        dma_band(64 * (t_lo + i) + 8 * wave);
+        dma_bandT(64 * (t_lo + i));
     }
     const int trow = tid >> 3, tch = tid & 7;   // this thread's 16-byte chunk of a [64][64] tile
     uint4 pk, pv, pkt;
@@ -540,7 +522,7 @@ __global__ __launch_bounds__(512) void relpos_bwd_dq_kernel(
         *reinterpret_cast<uint4*>(lds_kv[1] + offp) = pv;
     };
     auto lstore_kt = [&]() { *reinterpret_cast<uint4*>(lds_kv[2] + k_off(trow, tch)) = pkt; };
-    gload(0);
+    gload(t_lo);
     int qrow = q0 + c;
     const bool qvalid = qrow < T;
     qrow = qvalid ? qrow : T - 1;
@@ -569,7 +551,6 @@ __global__ __launch_bounds__(512) void relpos_bwd_dq_kernel(
     // inside the loop, behind -- and therefore also for -- the tile prefetch issued at the top of the iteration)
     asm volatile("" ::"v"(quf[0]), "v"(quf[1]), "v"(qvf[0]), "v"(qvf[1]), "v"(dof[0]), "v"(dof[1]), "v"(l2), "v"(dd));
     __syncthreads();
-    const int ntiles = (T + KVB - 1) / KVB;
     // dS^T slab of this (batch, head): [Tpad keys][Tpad queries] bf16; the 128-query block can overhang Tpad (a multiple of 64)
     const __amdgpu_buffer_rsrc_t rds = __builtin_amdgcn_make_buffer_rsrc((void*)(dSt + (size_t)bh * Tpad * Tpad), 0, Tpad * Tpad * 2, 0x00020000);
     // P^T slab, same layout (nullable): with it the dK / dV of this layer are two plain contractions over the queries of the stored
@@ -581,9 +562,11 @@ __global__ __launch_bounds__(512) void relpos_bwd_dq_kernel(
     // the even lane takes key rows r = 0, 1 of a block, the odd lane rows 2, 3 -- half the store instructions of 2-byte stores
     const bool odd = c & 1;
     const int dvo = (q0 + c < Tpad) ? ((8 * g + (odd ? 2 : 0)) * Tpad + q0 + (c & ~1)) * 2 : 0x7ffffff0;     // (Tpad is even: a pair is in or out together)
-    for (int t = 0; t < ntiles; ++t) {
+    for (int t = t_lo; t <= t_hi; ++t) {
         const int j0 = t * KVB;
-        const bool more = t + 1 < ntiles;
+        const bool more = t < t_hi;
+        // BAND: does the tile reach past the band of one of this wave's queries (wave-uniform)?
+        const bool wedge = BAND && !(j0 >= q0 + 15 - hw && j0 + KVB - 1 < q0 + hw);
         if (more) {   // tile t + 1: band rows / P^T columns n in [64 t + 192, 64 t + 256) replace the slot tile t - 1 retired
             dma_band(64 * t + 192 + 8 * wave);
             dma_bandT(64 * t + 192);
@@ -676,6 +659,10 @@ __global__ __launch_bounds__(512) void relpos_bwd_dq_kernel(
             for (int r = 0; r < 4; ++r) {
                 float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[kb][r], SCALE_LOG2E, -l2));   // invalid query: LSE = +inf
                 if (j0 + KVB > T) p = (j0 + 32 * (kb >> 1) + 4 * (kb & 1) + 8 * g + r < T) ? p : 0.f;   // last tile only
+                if (wedge) {      // out-of-band pair: P and dS are exact zeros (stored as such in the slabs)
+                    const int dj = j0 + 32 * (kb >> 1) + 4 * (kb & 1) + 8 * g + r - (q0 + c);
+                    p = (dj >= -hw && dj < hw) ? p : 0.f;
+                }
                 dp[kb][r] = p * (dp[kb][r] - dd);
                 st[kb][r] = p;
             }
@@ -764,6 +751,20 @@ __global__ __launch_bounds__(512) void relpos_bwd_dq_kernel(
     }
 }
 
+template <bool SF16, bool BAND>
+__global__ __launch_bounds__(512) void relpos_bwd_dq_kernel(
+    const bf16_t* __restrict__ Qu, const bf16_t* __restrict__ Qv, const bf16_t* __restrict__ K,
+    const bf16_t* __restrict__ Kt, const bf16_t* __restrict__ V, const bf16_t* __restrict__ P,
+    const bf16_t* __restrict__ Pt, const bf16_t* __restrict__ dOh, const float* __restrict__ LSE,
+    const float* __restrict__ Dv, bf16_t* __restrict__ dqkv, bf16_t* __restrict__ dSt, bf16_t* __restrict__ Pst, float* __restrict__ du,
+    float* __restrict__ dvb, int T, int Tpad, int H, int Rpad, const int* __restrict__ HW) {
+    if (BAND) {
+        const int hw = band_hw(HW, blockIdx.y % H);
+        if (hw < T) { relpos_bwd_dq_body<SF16, true>(Qu, Qv, K, Kt, V, P, Pt, dOh, LSE, Dv, dqkv, dSt, Pst, du, dvb, T, Tpad, H, Rpad, hw); return; }
+    }
+    relpos_bwd_dq_body<SF16, false>(Qu, Qv, K, Kt, V, P, Pt, dOh, LSE, Dv, dqkv, dSt, Pst, du, dvb, T, Tpad, H, Rpad, 0);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // backward kernel 1' (round 3): dK and dV from the dS^T / P^T slabs the dQ kernel stored -- two contractions over the queries,
 //   dK^T[d, key] = scale * sum_q Qu^T[d, q] dS^T[key, q]        dV^T[d, key] = sum_q dO^T[d, q] P^T[key, q]
@@ -777,10 +778,15 @@ __global__ __launch_bounds__(512) void relpos_bwd_dq_kernel(
 // (round 5: a rotated tile order per workgroup changes nothing -- not channel hot-spotting; three workgroups per CU instead of two
 //  (80 VGPRs) run 515-537 us against 421-427: more bytes in flight do not help, the slab walk -- 128 bytes from each of 128 rows 2 KiB
 //  apart per step -- is what the memory system delivers at 3.8 TB/s)
-__global__ __launch_bounds__(512) void relpos_bwd_dkdv_stream_kernel(const bf16_t* __restrict__ Qut, const bf16_t* __restrict__ dOt,
-                                                                     const bf16_t* __restrict__ dSt, const bf16_t* __restrict__ Pst,
-                                                                     bf16_t* __restrict__ dqkv, int T, int Tpad, int H) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][64 * 128];     // [stage][Qu^T | dO^T][d rows x 64 q]
+// BAND: the workgroup walks the query tiles that meet the band of one of its 128 keys; a wave (16 keys of ONE 64-key tile kt_w) reads
+// the slab rows of query tile t only where the dQ workgroup of those queries (128-query block t >> 1) visited key tile kt_w -- see
+// band_tile_lo / band_tile_hi: everything else in the slabs may be stale and is never read.
+__shared__ __attribute__((aligned(16))) unsigned char stream_lds[2][2][64 * 128];     // [stage][Qu^T | dO^T][d rows x 64 q]
+template <bool BAND>
+__device__ __forceinline__ void relpos_bwd_dkdv_stream_body(const bf16_t* __restrict__ Qut, const bf16_t* __restrict__ dOt,
+                                                            const bf16_t* __restrict__ dSt, const bf16_t* __restrict__ Pst,
+                                                            bf16_t* __restrict__ dqkv, int T, int Tpad, int H, const int hwv) {
+    auto& lds = stream_lds;
     const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
@@ -789,32 +795,45 @@ __global__ __launch_bounds__(512) void relpos_bwd_dkdv_stream_kernel(const bf16_
     const size_t hbt = (size_t)bh * HD * Tpad, sb = (size_t)bh * Tpad * Tpad + (size_t)krow * Tpad + 8 * g;
     const int trow = tid >> 3, tch = tid & 7;              // this thread's 16-byte chunk of a [64 d][64 q] tile
     const int ntiles = Tpad / 64;
+    const int J0 = blockIdx.x * 128, kt_w = (J0 + wave * 16) >> 6;
+    const int hw = hwv;
+    const int t_lo = BAND ? max(J0 - hw + 1, 0) >> 6 : 0;
+    const int t_hi = BAND ? min(J0 + 127 + hw, T - 1) >> 6 : ntiles - 1;
+    auto act = [&](int t) {       // wave-uniform
+        if (!BAND) return true;
+        const int I0 = (t >> 1) * 128;
+        return kt_w >= band_tile_lo(I0, hw) && kt_w <= band_tile_hi(I0, hw, T);
+    };
     uint4 ta, tb;
     s16x8_t fs[2], fp[2];
+    if (BAND) { fs[0] = fs[1] = fp[0] = fp[1] = s16x8_t{0, 0, 0, 0, 0, 0, 0, 0}; }
     // (one tile of slab rows in flight per wave; two were slower: 424 vs 402 us)
     auto gload = [&](int t) {
         ta = *reinterpret_cast<const uint4*>(Qut + hbt + (size_t)trow * Tpad + 64 * t + 8 * tch);
         tb = *reinterpret_cast<const uint4*>(dOt + hbt + (size_t)trow * Tpad + 64 * t + 8 * tch);
+        if (act(t)) {
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            fs[ks] = __builtin_nontemporal_load(reinterpret_cast<const s16x8_t*>(dSt + sb + 64 * t + 32 * ks));
-            fp[ks] = __builtin_nontemporal_load(reinterpret_cast<const s16x8_t*>(Pst + sb + 64 * t + 32 * ks));
+            for (int ks = 0; ks < 2; ++ks) {
+                fs[ks] = __builtin_nontemporal_load(reinterpret_cast<const s16x8_t*>(dSt + sb + 64 * t + 32 * ks));
+                fp[ks] = __builtin_nontemporal_load(reinterpret_cast<const s16x8_t*>(Pst + sb + 64 * t + 32 * ks));
+            }
         }
     };
     f32x4_t dk[4], dv[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { dk[i] = zero4; dv[i] = zero4; }
-    gload(0);
-    *reinterpret_cast<uint4*>(lds[0][0] + k_off(trow, tch)) = ta;
-    *reinterpret_cast<uint4*>(lds[0][1] + k_off(trow, tch)) = tb;
+    gload(t_lo);
+    *reinterpret_cast<uint4*>(lds[t_lo & 1][0] + k_off(trow, tch)) = ta;
+    *reinterpret_cast<uint4*>(lds[t_lo & 1][1] + k_off(trow, tch)) = tb;
     __syncthreads();
     const int swc = (c >> 1) & 7;
-    for (int t = 0; t < ntiles; ++t) {
+    for (int t = t_lo; t <= t_hi; ++t) {
         const int cur = t & 1;
         s16x8_t bs[2], bp[2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) { bs[ks] = fs[ks]; bp[ks] = fp[ks]; }
-        if (t + 1 < ntiles) gload(t + 1);
+        if (t < t_hi) gload(t + 1);
+        if (act(t)) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -823,7 +842,8 @@ __global__ __launch_bounds__(512) void relpos_bwd_dkdv_stream_kernel(const bf16_
                 dk[db] = mfma16x<false>(*reinterpret_cast<const s16x8_t*>(lds[cur][0] + ro), bs[ks], dk[db]);
                 dv[db] = mfma16x<false>(*reinterpret_cast<const s16x8_t*>(lds[cur][1] + ro), bp[ks], dv[db]);
             }
-        if (t + 1 < ntiles) {
+        }
+        if (t < t_hi) {
             *reinterpret_cast<uint4*>(lds[cur ^ 1][0] + k_off(trow, tch)) = ta;     // the other stage: last read before the previous barrier
             *reinterpret_cast<uint4*>(lds[cur ^ 1][1] + k_off(trow, tch)) = tb;
             __syncthreads();
@@ -844,16 +864,33 @@ __global__ __launch_bounds__(512) void relpos_bwd_dkdv_stream_kernel(const bf16_
     }
 }
 
+template <bool BAND>
+__global__ __launch_bounds__(512) void relpos_bwd_dkdv_stream_kernel(const bf16_t* __restrict__ Qut, const bf16_t* __restrict__ dOt,
+                                                                     const bf16_t* __restrict__ dSt, const bf16_t* __restrict__ Pst,
+                                                                     bf16_t* __restrict__ dqkv, int T, int Tpad, int H,
+                                                                     const int* __restrict__ HW) {
+    if (BAND) {
+        const int hw = band_hw(HW, blockIdx.y % H);
+        if (hw < T) { relpos_bwd_dkdv_stream_body<true>(Qut, dOt, dSt, Pst, dqkv, T, Tpad, H, hw); return; }
+    }
+    relpos_bwd_dkdv_stream_body<false>(Qut, dOt, dSt, Pst, dqkv, T, Tpad, H, 0);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // backward kernel 3: dP[r, h*64 + d] += scale * sum_{b, i} dS_b[i, i + r - (T-1)] * Qv_b[i, d]
 //   grid (Rpad/64, H, Bsplit); each workgroup: one 64-row block of r, loops over its batch slice and all i tiles.
 //   dS^T tile staged with a 33-word row stride so that the diagonal gather is bank-conflict free.
 // ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void relpos_bwd_dp_kernel(const bf16_t* __restrict__ dSt, const bf16_t* __restrict__ Qvt,
-                                                            float* __restrict__ dP, int B, int T, int Tpad, int H,
-                                                            int ldp, int nrb, int bsplit) {
-    __shared__ __attribute__((aligned(16))) unsigned int lds_s[2][128 * 33];
-    __shared__ __attribute__((aligned(16))) unsigned char lds_q[2][KVB * 128];
+// BAND: only the rows r = j - i + T - 1 with -hw <= j - i < hw can be non-zero: a workgroup whose 64 rows hold none of them does
+// nothing; the others read a dS^T tile only where the dQ kernel visited it (band_tile_lo / band_tile_hi), zeros elsewhere.
+__shared__ __attribute__((aligned(16))) unsigned int dp_lds_s[2][128 * 33];
+__shared__ __attribute__((aligned(16))) unsigned char dp_lds_q[2][KVB * 128];
+template <bool BAND>
+__device__ __forceinline__ void relpos_bwd_dp_body(const bf16_t* __restrict__ dSt, const bf16_t* __restrict__ Qvt,
+                                                   float* __restrict__ dP, int B, int T, int Tpad, int H,
+                                                   int ldp, int nrb, int bsplit, const int hwv) {
+    auto& lds_s = dp_lds_s;
+    auto& lds_q = dp_lds_q;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lg = lane >> 5;
     // XCD-contiguous order with the r block fastest: neighbouring r blocks of one (head, batch slice) read overlapping key rows of the
     // same dS^T tiles (128 rows for 64 diagonals), so they should share an L2
@@ -872,6 +909,9 @@ __global__ __launch_bounds__(256) void relpos_bwd_dp_kernel(const bf16_t* __rest
     t_lo = t_lo < 0 ? 0 : t_lo;
     t_hi = t_hi > ntiles - 1 ? ntiles - 1 : t_hi;
     const int nt = t_hi - t_lo + 1;
+    const int hw = hwv;
+    const int d0 = R0 - (T - 1);                 // j - i of the workgroup's first row
+    if (BAND && !(d0 + 63 >= -hw && d0 < hw)) return;
     const int total = (nt > 0 && b_end > b_begin) ? nt * (b_end - b_begin) : 0;
     // the next (batch, query tile) pair travels HBM -> registers while the current one is multiplied, registers -> the other LDS stage
     // afterwards (one barrier per pair; the first version loaded, stored and multiplied in sequence and spent 77 % of its wave
@@ -881,12 +921,13 @@ __global__ __launch_bounds__(256) void relpos_bwd_dp_kernel(const bf16_t* __rest
     auto gload = [&](int it) {
         const int bb = it / nt, t = t_lo + (it - bb * nt);
         const int bh = (b_begin + bb) * H + h, i0 = t * 64, jbase = i0 + R0 - (T - 1);
+        const int kt_lo = BAND ? band_tile_lo((t >> 1) * 128, hw) : 0, kt_hi = BAND ? band_tile_hi((t >> 1) * 128, hw, T) : 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int j = jbase + (tid >> 3) + 32 * i;
             const int jc = j < 0 ? 0 : (j < T ? j : T - 1);
             const uint4 v = *reinterpret_cast<const uint4*>(dSt + ((size_t)bh * Tpad + jc) * Tpad + i0 + (tid & 7) * 8);
-            const bool ok = j >= 0 && j < T;
+            const bool ok = j >= 0 && j < T && (!BAND || ((jc >> 6) >= kt_lo && (jc >> 6) <= kt_hi));
             pv[i] = make_uint4(ok ? v.x : 0u, ok ? v.y : 0u, ok ? v.z : 0u, ok ? v.w : 0u);
         }
         tile_gload(rq, Qvt + (size_t)bh * HD * Tpad, 0, HD, Tpad, i0, tid);
@@ -929,16 +970,29 @@ __global__ __launch_bounds__(256) void relpos_bwd_dp_kernel(const bf16_t* __rest
     }
 }
 
+template <bool BAND>
+__global__ __launch_bounds__(256) void relpos_bwd_dp_kernel(const bf16_t* __restrict__ dSt, const bf16_t* __restrict__ Qvt,
+                                                            float* __restrict__ dP, int B, int T, int Tpad, int H,
+                                                            int ldp, int nrb, int bsplit, const int* __restrict__ HW) {
+    if (BAND) {
+        const int hw = band_hw(HW, (xcd_remap(blockIdx.x, nrb * H * bsplit) / nrb) % H);      // (the head of this workgroup, as in the body)
+        if (hw < T) { relpos_bwd_dp_body<true>(dSt, Qvt, dP, B, T, Tpad, H, ldp, nrb, bsplit, hw); return; }
+    }
+    relpos_bwd_dp_body<false>(dSt, Qvt, dP, B, T, Tpad, H, ldp, nrb, bsplit, 0);
+}
+
 // the pre-pass (D = rowsum(dO * O), head-split dO copies) is shared with the encoder attention
 extern "C" int sed_mhsa_bwd_prep(const void* dO, const void* O, float* Dtmp, void* dOh, void* dOt, int B, int H, int N,
                                  int Npad, int o_f16, hipStream_t stream);
 
-extern "C" int sed_relpos_attn_bwd(const void* Qu, const void* Qut, const void* Qv, const void* Qvt, const void* K,
-                                   const void* Kt, const void* V, const void* P, const void* Pt, const void* O,
-                                   const void* dO, const float* LSE, float* Dtmp, void* dOh, void* dOt, void* dqkv,
-                                   void* dSt, void* Pst, float* dP, float* du, float* dv, int B, int H, int T, int Tpad,
-                                   int Rpad, int need_param_grads, int f16, int o_kind, hipStream_t stream) {
+template <bool BAND>
+static int relpos_attn_bwd(const void* Qu, const void* Qut, const void* Qv, const void* Qvt, const void* K,
+                           const void* Kt, const void* V, const void* P, const void* Pt, const void* O,
+                           const void* dO, const float* LSE, float* Dtmp, void* dOh, void* dOt, void* dqkv,
+                           void* dSt, void* Pst, float* dP, float* du, float* dv, int B, int H, int T, int Tpad,
+                           int Rpad, int need_param_grads, int f16, int o_kind, const int* hw, hipStream_t stream) {
     (void)hipGetLastError();
+    if (BAND && hw == nullptr) return SED_ERR_ARG;
     // f16 != 0: Qu, Qv, K, P (score recompute) are IEEE half; Qut, Qvt, Kt, V, Pt, dO are bf16.
     // o_kind: storage type of O (0 bf16, 1 f16, 2 f32).
     if (T <= 0 || (T % 8) || Tpad % 64 || Tpad < T || Rpad % 64 || Rpad < 2 * T - 1) return SED_ERR_ARG;
@@ -948,22 +1002,43 @@ extern "C" int sed_relpos_attn_bwd(const void* Qu, const void* Qut, const void* 
     // Pst (nullable): a second [B H, Tpad, Tpad] bf16 slab, zero outside its valid region like dSt.  With it the dQ kernel also stores
     // P^T and dK / dV come from the streaming kernel; without it the first-generation kernel recomputes the scores for them.
 #define SED_LAUNCH_RP(F)                                                                                               \
-    if (Pst == nullptr)                                                                                                \
+    if (Pst == nullptr && BAND)                                                                                        \
+        hipLaunchKernelGGL(relpos_bwd_dkdv_band_kernel<F>, grid, dim3(256), 0, stream, (const bf16_t*)Qu, (const bf16_t*)Qut, \
+                           (const bf16_t*)Qv, (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)P, (const bf16_t*)dOh, \
+                           (const bf16_t*)dOt, LSE, Dtmp, (bf16_t*)dqkv, T, Tpad, H, Rpad, hw);                        \
+    else if (Pst == nullptr)                                                                                           \
         hipLaunchKernelGGL(relpos_bwd_dkdv_kernel<F>, grid, dim3(256), 0, stream, (const bf16_t*)Qu, (const bf16_t*)Qut, \
                            (const bf16_t*)Qv, (const bf16_t*)K, (const bf16_t*)V, (const bf16_t*)P, (const bf16_t*)dOh, \
                            (const bf16_t*)dOt, LSE, Dtmp, (bf16_t*)dqkv, T, Tpad, H, Rpad);                            \
-    hipLaunchKernelGGL(relpos_bwd_dq_kernel<F>, grid, dim3(512), DQ16_LDS, stream, (const bf16_t*)Qu, (const bf16_t*)Qv,    \
+    hipLaunchKernelGGL((relpos_bwd_dq_kernel<F, BAND>), grid, dim3(512), DQ16_LDS, stream, (const bf16_t*)Qu, (const bf16_t*)Qv,    \
                        (const bf16_t*)K, (const bf16_t*)Kt, (const bf16_t*)V, (const bf16_t*)P, (const bf16_t*)Pt,     \
-                       (const bf16_t*)dOh, LSE, Dtmp, (bf16_t*)dqkv, (bf16_t*)dSt, (bf16_t*)Pst, du, dv, T, Tpad, H, Rpad);
+                       (const bf16_t*)dOh, LSE, Dtmp, (bf16_t*)dqkv, (bf16_t*)dSt, (bf16_t*)Pst, du, dv, T, Tpad, H, Rpad, hw);
     if (f16) { SED_LAUNCH_RP(true) } else { SED_LAUNCH_RP(false) }
 #undef SED_LAUNCH_RP
     if (Pst != nullptr)
-        hipLaunchKernelGGL(relpos_bwd_dkdv_stream_kernel, grid, dim3(512), 0, stream, (const bf16_t*)Qut, (const bf16_t*)dOt,
-                           (const bf16_t*)dSt, (const bf16_t*)Pst, (bf16_t*)dqkv, T, Tpad, H);
+        hipLaunchKernelGGL(relpos_bwd_dkdv_stream_kernel<BAND>, grid, dim3(512), 0, stream, (const bf16_t*)Qut, (const bf16_t*)dOt,
+                           (const bf16_t*)dSt, (const bf16_t*)Pst, (bf16_t*)dqkv, T, Tpad, H, hw);
     if (need_param_grads) {
         int bsplit = B < 8 ? B : 8;
-        hipLaunchKernelGGL(relpos_bwd_dp_kernel, dim3((Rpad / 64) * H * bsplit), dim3(256), 0, stream, (const bf16_t*)dSt,
-                           (const bf16_t*)Qvt, dP, B, T, Tpad, H, H * HD, Rpad / 64, bsplit);
+        hipLaunchKernelGGL(relpos_bwd_dp_kernel<BAND>, dim3((Rpad / 64) * H * bsplit), dim3(256), 0, stream, (const bf16_t*)dSt,
+                           (const bf16_t*)Qvt, dP, B, T, Tpad, H, H * HD, Rpad / 64, bsplit, hw);
     }
     return sed_check_launch();
+}
+extern "C" int sed_relpos_attn_bwd(const void* Qu, const void* Qut, const void* Qv, const void* Qvt, const void* K,
+                                   const void* Kt, const void* V, const void* P, const void* Pt, const void* O,
+                                   const void* dO, const float* LSE, float* Dtmp, void* dOh, void* dOt, void* dqkv,
+                                   void* dSt, void* Pst, float* dP, float* du, float* dv, int B, int H, int T, int Tpad,
+                                   int Rpad, int need_param_grads, int f16, int o_kind, hipStream_t stream) {
+    return relpos_attn_bwd<false>(Qu, Qut, Qv, Qvt, K, Kt, V, P, Pt, O, dO, LSE, Dtmp, dOh, dOt, dqkv, dSt, Pst, dP, du, dv, B, H, T, Tpad,
+                                  Rpad, need_param_grads, f16, o_kind, nullptr, stream);
+}
+extern "C" int sed_relpos_attn_band_bwd(const void* Qu, const void* Qut, const void* Qv, const void* Qvt, const void* K,
+                                        const void* Kt, const void* V, const void* P, const void* Pt, const void* O,
+                                        const void* dO, const float* LSE, float* Dtmp, void* dOh, void* dOt, void* dqkv,
+                                        void* dSt, void* Pst, float* dP, float* du, float* dv, int B, int H, int T, int Tpad,
+                                        int Rpad, int need_param_grads, int f16, int o_kind, const int32_t* half_width,
+                                        hipStream_t stream) {
+    return relpos_attn_bwd<true>(Qu, Qut, Qv, Qvt, K, Kt, V, P, Pt, O, dO, LSE, Dtmp, dOh, dOt, dqkv, dSt, Pst, dP, du, dv, B, H, T, Tpad,
+                                 Rpad, need_param_grads, f16, o_kind, half_width, stream);
 }

@@ -57,6 +57,17 @@ def _fused_step_moves_versions(optimizer, args, kwargs):
 register_optimizer_step_post_hook(_fused_step_moves_versions)
 
 
+def band_half_width(model, dev, T):
+    """The context network's local window (PaSST_SED(decoder_win_len=...)) as the band kernels take it: int32 [H] on `dev`, made once
+    per device; None without a window.  The reference's mask has side decoder_pos_emd_len and fails at any other length."""
+    dec = model.decoder
+    if dec.half_widths is None:
+        return None
+    if T != dec.seq_len:
+        raise RuntimeError(f"decoder_win_len: the attention mask has side {dec.seq_len} (decoder_pos_emd_len), the sequence has {T} frames")
+    return dec.half_width_tensor(dev)
+
+
 def window_starts(n_in=1000, win=512, step=49):
     """src/models/encoder_slide_window.py:27."""
     return list(range(0, n_in + step - win, step))
@@ -617,6 +628,7 @@ class SedEngine:
                     return self._decoder_fwd(W, x, save)
             finally:
                 self._in_split = False
+        hwt = band_half_width(m, dev, T)
         for li in range(m.decoder_layer_num):
             p = f"decoder.encoder_blocks.{li}."
             in_scale = math.sqrt(D) if li == 0 else 1.0
@@ -661,7 +673,10 @@ class SedEngine:
             o16 = E(M, D, dt=F32 if SP else A16)
             lse = E(B * H, T)
             o16s = E(M, 3 * D, dt=F16) if SP else None      # split-precision image of the attention output, written by the kernel itself
-            call("sed_relpos_attn_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0)
+            if hwt is None:
+                call("sed_relpos_attn_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0)
+            else:       # local window (decoder_win_len): the band kernels skip the key tiles no query of a workgroup sees
+                call("sed_relpos_attn_band_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0, hwt)
             x1 = E(B, T, D)
             gemm_nt(o16s if SP else o16, wk(p + "attn.out_proj.weight"), EPI_F32_RESID,
                     bias=self.P(p + "attn.out_proj.bias"), res=y32, outF=x1)
@@ -1220,10 +1235,13 @@ class SedEngine:
             dv = Gl(p + "attn.pos_bias_v")
             scratch_uv = Z(2, D)
             f16 = is_f16(L["qu"])
-            call("sed_relpos_attn_bwd", L["qu"], to_bf16_(L["qut"]), L["qv"], to_bf16_(L["qvt"]), L["k"],
-                 to_bf16_(L["kt"]), to_bf16_(L["v"]), L["Ph"], to_bf16_(L["Pt"]), L["o16"], do16, L["lse"], Dtmp, dOh, dOt,
-                 dqkv, dSt, Pst, dP, du if du is not None else scratch_uv[0], dv if dv is not None else scratch_uv[1], B, H, T,
-                 Tpad, Rpad, 1 if trainable else 0, f16, o_kind(L["o16"]))
+            # (local window: the pooled slabs may hold the full-window content of an earlier call outside the band -- the band kernels
+            #  neither write nor read those tiles, see relpos_attention.hip band_tile_lo / band_tile_hi)
+            hwt = band_half_width(m, dev, T)
+            call("sed_relpos_attn_bwd" if hwt is None else "sed_relpos_attn_band_bwd", L["qu"], to_bf16_(L["qut"]), L["qv"],
+                 to_bf16_(L["qvt"]), L["k"], to_bf16_(L["kt"]), to_bf16_(L["v"]), L["Ph"], to_bf16_(L["Pt"]), L["o16"], do16, L["lse"],
+                 Dtmp, dOh, dOt, dqkv, dSt, Pst, dP, du if du is not None else scratch_uv[0], dv if dv is not None else scratch_uv[1],
+                 B, H, T, Tpad, Rpad, 1 if trainable else 0, f16, o_kind(L["o16"]), *(() if hwt is None else (hwt,)))
             del dSt, Pst, dOh, dOt, do16
             if trainable:
                 dPT = E(D, Rpad, dt=BF16)

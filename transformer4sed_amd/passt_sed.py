@@ -8,6 +8,7 @@ names (so `state_dict()` interchanges with reference checkpoints and `recipes/de
 parameter containers only; their torch `forward`s are never used.
 """
 import math
+from collections.abc import Sequence
 
 import torch
 import torch.nn as nn
@@ -141,11 +142,61 @@ class _XLBlock(_Holder):
         self.mlp = _Mlp(dim, dim)  # mlp_ratio 1 (src/models/transformer_decoder.py:84,91)
 
 
+def band_half_widths(win_len, heads):
+    """`decoder_win_len` (an int, or one int per head: transformer_decoder.py:96-103) -> the per-head half widths hw = w // 2 of
+    mask.py:7-23.  A width below 2 masks whole rows (the reference then yields NaN) and is refused."""
+    if isinstance(win_len, bool) or not isinstance(win_len, (int, Sequence)) or isinstance(win_len, (str, bytes)):
+        raise TypeError(f"decoder_win_len must be an int or a sequence of {heads} ints, got {win_len!r}")
+    per_head = not isinstance(win_len, int)
+    widths = list(win_len) if per_head else [win_len] * heads
+    if len(widths) != heads:
+        raise ValueError(f"decoder_win_len: {len(widths)} widths for {heads} heads")
+    if any(isinstance(w, bool) or not isinstance(w, int) for w in widths):
+        raise TypeError(f"decoder_win_len must hold ints, got {win_len!r}")
+    if any(w < 2 for w in widths):
+        raise ValueError(f"decoder_win_len: a width below 2 masks whole rows of the attention matrix (NaN in the reference), got {win_len!r}")
+    return [w // 2 for w in widths], per_head
+
+
+def band_mask(seq_len, hw):
+    """mask.py:7-23 `diagonal_mask(seq_len, w)` in closed form for hw = w // 2: True = masked; query i sees the keys
+    max(0, i - hw) <= j < min(seq_len, i + hw) -- hw to the left, itself, hw - 1 to the right."""
+    i = torch.arange(seq_len).unsqueeze(1)
+    j = torch.arange(seq_len).unsqueeze(0)
+    return ~((j >= i - hw) & (j < i + hw))
+
+
 class _Decoder(_Holder):
-    def __init__(self, dim, layers, heads):
+    def __init__(self, dim, layers, heads, seq_len=1000, win_len=None):
         super().__init__()
         self.encoder_blocks = nn.ModuleList([_XLBlock(dim, heads) for _ in range(layers)])
-        self.att_mask = None
+        self.seq_len = seq_len
+        self.half_widths = None          # per-head hw (ints) when a local window is set
+        self._hw_dev = {}                # device -> int32 [heads], what the band kernels read
+        mask = None
+        if win_len is not None:
+            self.half_widths, per_head = band_half_widths(win_len, heads)
+            mask = torch.stack([band_mask(seq_len, hw) for hw in self.half_widths]) if per_head else band_mask(seq_len, self.half_widths[0])
+        # the reference's persistent buffer (transformer_decoder.py:108): [T, T] or [heads, T, T] bool, absent from the state_dict
+        # without a window.  Checkpoint interchange only -- the kernels take the band from `half_widths`.
+        self.register_buffer("att_mask", mask)
+
+    def half_width_tensor(self, dev):
+        t = self._hw_dev.get(dev)
+        if t is None:
+            t = self._hw_dev[dev] = torch.tensor(self.half_widths, dtype=torch.int32, device=dev)
+        return t
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        key = prefix + "att_mask"
+        got = state_dict.get(key)
+        if self.att_mask is not None and got is not None and tuple(got.shape) == tuple(self.att_mask.shape) \
+                and not torch.equal(got.to(self.att_mask.device, torch.bool), self.att_mask):
+            error_msgs.append(f"{key} is not the diagonal band of this model's decoder_win_len: the attention kernels express "
+                              "diagonal bands only (hw = w // 2 keys to the left, hw - 1 to the right)")
+            state_dict = {k: v for k, v in state_dict.items() if k != key}
+            state_dict[key] = self.att_mask
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
 
 class _AttnPool(_Holder):
@@ -243,7 +294,6 @@ class PaSST_SED(SEDModel):
             if lora_config is not None: unsupported.append("LoRA")
         if decoder != "transformerXL": unsupported.append(f"decoder={decoder!r}")
         if s_patchout_f or s_patchout_t: unsupported.append("patchout")
-        if decoder_win_len is not None: unsupported.append("decoder_win_len")
         if interpolate_mode != "linear": unsupported.append(f"interpolate_mode={interpolate_mode!r}")
         if unsupported:
             raise NotImplementedError("the HIP MAT-SED path covers the MAT-SED configs only; unsupported: "
@@ -287,7 +337,7 @@ class PaSST_SED(SEDModel):
             if mlm_dict["out_dim"] != D:
                 raise NotImplementedError("mlm out_dim != 768")
         self.decoder_layer_num = decoder_layer_num
-        self.decoder = _Decoder(decoder_dim, decoder_layer_num, H)
+        self.decoder = _Decoder(decoder_dim, decoder_layer_num, H, seq_len=decoder_pos_emd_len, win_len=decoder_win_len)
         self.classifier = nn.Linear(decoder_dim, class_num)
         self.has_at = bool(at_adapter)
         self.at_adpater = at_adapter  # (sic) spelling is part of the checkpoint contract

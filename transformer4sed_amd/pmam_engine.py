@@ -20,7 +20,7 @@ import torch
 
 from . import ops
 
-from .engine import SedEngine, _W, D, H, version_key
+from .engine import SedEngine, _W, D, H, version_key, band_half_width
 from .ops import BF16, F16, F32, call, h2d, gemm_nt, gemm_nt_cols, gemm_dw, gemm_dw_tn, dw_tn_ok, pad64, transpose_bf16, split3, is_f16, to_bf16_, o_kind
 from .ops import EPI_F32, EPI_F32_RESID, EPI_BF16, EPI_GELU32
 
@@ -414,6 +414,7 @@ class PmamEngine(SedEngine):
                     return self._decoder_fwd(W, x, save)
             finally:
                 self._in_split = False
+        hwt = band_half_width(m, dev, T)
         for li in range(m.decoder_layer_num):
             p = f"decoder.encoder_blocks.{li}."
             aux = self.dec_aux[li]
@@ -444,7 +445,10 @@ class PmamEngine(SedEngine):
             o32 = E(M, Dp)
             lse = E(B * H, T)
             o32s = E(M, 3 * Dp, dt=F16)
-            call("sed_relpos_attn_fwd", qu, qv, k, vt, Ph, o32, o32s, lse, B, H, T, Tpad, Rpad, 1, 1)
+            if hwt is None:
+                call("sed_relpos_attn_fwd", qu, qv, k, vt, Ph, o32, o32s, lse, B, H, T, Tpad, Rpad, 1, 1)
+            else:       # local window (decoder_win_len)
+                call("sed_relpos_attn_band_fwd", qu, qv, k, vt, Ph, o32, o32s, lse, B, H, T, Tpad, Rpad, 1, 1, hwt)
             x1 = E(B, T, Dd)
             gemm_nt(o32s, W[p + "attn.out_proj.weight"].ws, EPI_F32_RESID, bias=self.P(p + "attn.out_proj.bias"), res=y32,
                     outF=x1)
@@ -840,9 +844,11 @@ class PmamEngine(SedEngine):
             Pst = self._zeros(("Pst", B, Tpad), (B * H, Tpad, Tpad), BF16, dev) if self.relpos_stream else None
             dP = Z(Rpad, Dp)
             du, dv = (slots[("du", li)], slots[("dv", li)]) if trainable else (Z(Dp), Z(Dp))
-            call("sed_relpos_attn_bwd", L["qu"], to_bf16_(L["qut"]), L["qv"], to_bf16_(L["qvt"]), L["k"], to_bf16_(L["kt"]),
-                 to_bf16_(L["v"]), L["Ph"], to_bf16_(L["Pt"]), L["o16"], do16, L["lse"], Dtmp, dOh, dOt, dqkv, dSt, Pst, dP, du, dv, B, H,
-                 T, Tpad, Rpad, 1 if trainable else 0, 1, o_kind(L["o16"]))
+            hwt = band_half_width(m, dev, T)
+            call("sed_relpos_attn_bwd" if hwt is None else "sed_relpos_attn_band_bwd", L["qu"], to_bf16_(L["qut"]), L["qv"],
+                 to_bf16_(L["qvt"]), L["k"], to_bf16_(L["kt"]), to_bf16_(L["v"]), L["Ph"], to_bf16_(L["Pt"]), L["o16"], do16, L["lse"],
+                 Dtmp, dOh, dOt, dqkv, dSt, Pst, dP, du, dv, B, H, T, Tpad, Rpad, 1 if trainable else 0, 1, o_kind(L["o16"]),
+                 *(() if hwt is None else (hwt,)))
             del dSt, Pst, dOh, dOt, do16
             if trainable:
                 # gradient images (padded heads) in the zeroed slots of `_grad_slots`; one scatter launch after the loop un-pads them
