@@ -543,6 +543,28 @@ int sed_colsum_f32(const float* x, float* out, int rows, int cols, int64_t ld, h
 int sed_sup_loss(const float* pred, const float* target, float* loss, float* grad, int64_t n, int kind, float gamma_pos, float gamma_neg,
                  float margin, hipStream_t stream);
 
+/* ------------------------------------------------------------------ Conformer context network (csrc/conformer.hip) */
+/* The middle of ConvolutionModule.forward (src/models/transformer/conformer.py:242-270) in one pass: x [B T, 2 C] fp32 (pointwise_conv1's
+ * output, bias applied) -> u = a * sigmoid(g) (a = columns 0 .. C-1, g = C .. 2C-1) -> c[t] = bias + sum_k w[k] u[t + k - 15] (w [C, 31],
+ * zeros outside 0 <= t + k - 15 < T of the same clip) -> LayerNorm over C (gamma, beta, eps) -> y = n * sigmoid(n).  C = 768.
+ * y16 (nullable): the operand image of the pointwise_conv2 GEMM, mode 0 bf16 [B T, C], 1 f16, 4 split precision f16 [B T, 3 C] =
+ * [hi | lo | hi] (as sed_layernorm_fwd writes it); y32 (nullable): fp32 [B T, C].  conv / mean / rstd (nullable together): the
+ * convolution output fp32 [B T, C] and the LayerNorm statistics [B T], what sed_conv_glu_dw_bwd reads. */
+int sed_conv_glu_dw_fwd(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, float eps, void* y16,
+                        float* y32, float* conv, float* mean, float* rstd, int B, int T, int C, int mode, hipStream_t stream);
+/* Its backward: dy fp32 [B T, C] -> dx16 = bf16 [B T, 2 C] (gradient of pointwise_conv1's output), and dw [C, 31], dbias, dgamma,
+ * dbeta [C] (each nullable) += their gradients.  Those four are sums over all frames, taken in a fixed order (per-workgroup partials in
+ * `partials`, then one pass over them): the same bits in every run.  partials: scratch of min(B * ceil(T / 20), 256) * 34 * C floats. */
+int sed_conv_glu_dw_bwd(const float* dy, const float* x, const float* conv, const float* mean, const float* rstd, const float* w,
+                        const float* gamma, const float* beta, void* dx16, float* dw, float* dbias, float* dgamma, float* dbeta,
+                        float* partials, int64_t partial_floats, int B, int T, int C, hipStream_t stream);
+/* Swish of the feed-forwards (conformer.py:46-58,147-152): h fp32 [M, C] -> operand image of h * sigmoid(h) (y16, mode as above; nullable)
+ * and / or its fp32 value (y32, nullable);  backward: dh16 = bf16(dy * Swish'(h)) over n elements (n % 4 == 0) */
+int sed_swish_fwd(const float* h, void* y16, float* y32, int M, int C, int mode, hipStream_t stream);
+int sed_swish_bwd(const float* dy, const float* h, void* dh16, int64_t n, hipStream_t stream);
+/* out = res + scale * in over n fp32 elements (n % 4 == 0; res nullable; out may alias in or res), out16 (nullable) = bf16 of the result */
+int sed_scale_add_f32(const float* in, const float* res, float* out, void* out16, int64_t n, float scale, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,6 +277,13 @@ class SedEngine:
             p = f"backbone.blocks.{i}."
             names += [p + "attn.qkv.weight", p + "attn.proj.weight", p + "mlp.fc1.weight", p + "mlp.fc2.weight"]
         for i in range(m.decoder_layer_num):
+            if m.decoder_name == "conformer":       # (the 1-tap Conv1d weights [out, in, 1] are [out, in] matrices to the image kernel)
+                p = f"decoder.blocks.{i}."
+                names += [p + "self_attn.in_proj.weight", p + "self_attn.out_proj.weight", p + "self_attn.linear_pos.weight",
+                          p + "feed_forward_macaron.0.weight", p + "feed_forward_macaron.3.weight",
+                          p + "conv_module.pointwise_conv1.weight", p + "conv_module.pointwise_conv2.weight",
+                          p + "feed_forward.0.weight", p + "feed_forward.3.weight"]
+                continue
             p = f"decoder.encoder_blocks.{i}."
             names += [p + "attn.in_proj.weight", p + "attn.out_proj.weight", p + "attn.linear_pos.weight",
                       p + "mlp.fc1.weight", p + "mlp.fc2.weight"]
@@ -710,6 +717,130 @@ class SedEngine:
             cur = x2
         return cur, ctx
 
+    # ------------------------------------------------------------------ context network, decoder="conformer"
+    def _swish_ffn_fwd(self, W, ff, norm, xin, M, save):
+        """xin + 0.5 * Linear(Swish(Linear(LayerNorm(xin)))) (conformer.py:98-101,134-137); `ff` / `norm`: parameter prefixes.  Returns the
+        new stream [M, D] fp32 and what `_swish_ffn_bwd` reads."""
+        dev = xin.device
+        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        SP = self.split
+        f16 = 1 if self.act == F16 else 0
+        img = lambda: E(M, 3 * D, dt=F16) if SP else E(M, D, dt=self.act)
+        wk = (lambda n: W[n].ws) if SP else (lambda n: W[n].w)
+        y = img()
+        mean, rstd = (E(M), E(M)) if save else (None, None)
+        call("sed_layernorm_fwd", xin, self.P(norm + ".weight"), self.P(norm + ".bias"), 1e-5, 1.0, y, None, mean, rstd, M, D, 4 if SP else f16)
+        h = E(M, D)
+        gemm_nt(y, wk(ff + ".0.weight"), EPI_F32, bias=self.P(ff + ".0.bias"), outF=h)
+        a = img()
+        call("sed_swish_fwd", h, a, None, M, D, 4 if SP else f16)
+        out = E(M, D)
+        gemm_nt(a, wk(ff + ".3.weight"), EPI_F32, bias=self.P(ff + ".3.bias"), outF=out)
+        call("sed_scale_add_f32", out, xin, out, None, M * D, 0.5)
+        return out, (dict(x_in=xin, y=y, mean=mean, rstd=rstd, h=h, a=a) if save else None)
+
+    def _conformer_fwd(self, W, x, save):
+        """ConformerDecoder (src/models/transformer_decoder.py:157-165, conformer.py:75-144).  x [B,T,D] f32.  Per block, on the residual
+        stream s (which starts as sqrt(D) x: RelPositionalEncoding's scaling is applied to the stream itself here):
+            s += 0.5 ffn_macaron(norm_ff_macaron(s));  s += relattn(norm_mha(s));  s += conv_module(norm_conv(s));
+            s += 0.5 ffn(norm_ff(s));  s = norm_final(s)
+        The attention is the Transformer-XL block's (same kernels, same split-precision terms, same local window)."""
+        m = self.m
+        dev = x.device
+        B, T, _ = x.shape
+        Tpad = pad64(T)
+        M = B * T
+        SP = self.split
+        if SP and not getattr(self, "_in_split", False):
+            self._in_split = True
+            try:
+                with ops.split_precision():
+                    return self._conformer_fwd(W, x, save)
+            finally:
+                self._in_split = False
+        pos16, posT16, Rpad = self._pos(T, dev, want_plain=M >= 1024)
+        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        A16 = self.act
+        f16 = 1 if A16 == F16 else 0
+        mode = 4 if SP else f16
+        img = lambda: E(M, 3 * D, dt=F16) if SP else E(M, D, dt=A16)
+        wk = (lambda n: W[n].ws) if SP else (lambda n: W[n].w)
+        KD = 3 * D if SP else D
+        ctx = dict(B=B, T=T, Tpad=Tpad, Rpad=Rpad, layers=[])
+        hwt = band_half_width(m, dev, T)
+        cur = E(M, D)
+        call("sed_scale_add_f32", x, None, cur, None, M * D, math.sqrt(D))
+        for li in range(m.decoder_layer_num):
+            p = f"decoder.blocks.{li}."
+            pa = p + "self_attn."
+            x1, ffm = self._swish_ffn_fwd(W, p + "feed_forward_macaron", p + "norm_ff_macaron", cur, M, save)
+            # ---- attention: x2 = x1 + out_proj(relattn(norm_mha(x1)))
+            T2 = SP and self.dec_terms2 and M >= 1024
+            y16 = E(M, 3 * D, dt=F16) if (SP and not T2) else E(M, D, dt=A16)
+            mean1, rstd1 = (E(M), E(M)) if save else (None, None)
+            call("sed_layernorm_fwd", x1, self.P(p + "norm_mha.weight"), self.P(p + "norm_mha.bias"), 1e-5, 1.0, y16, None, mean1, rstd1,
+                 M, D, 4 if (SP and not T2) else f16)
+            Ph = E(H, Rpad, 64, dt=A16)
+            Pt = torch.zeros(H, 64, Rpad, dtype=A16, device=dev) if save else None
+            ptmp = E(Rpad, D, dt=A16)
+            if T2:
+                with ops.plain_precision():
+                    gemm_nt(pos16, W[pa + "linear_pos.weight"].w, EPI_BF16, outH=ptmp)
+            else:
+                gemm_nt(pos16, wk(pa + "linear_pos.weight"), EPI_BF16, outH=ptmp)
+            Ph.copy_(ptmp.view(Rpad, H, 64).permute(1, 0, 2))
+            if save:
+                Pt.copy_(ptmp.view(Rpad, H, 64).permute(1, 2, 0))
+            B16 = BF16 if save else A16
+            qu, k = [E(B * H, T, 64, dt=A16) for _ in range(2)]
+            v = E(B * H, T, 64, dt=B16)
+            qv = E(B * H, T, 64, dt=A16)
+            use_pool = getattr(self, "_lease_ok", False) or not save
+            vt = self._zeros(("dec_vt", li, B, Tpad), (B * H, 64, Tpad), A16, dev, use_pool)
+            qut = kt = qvt = None
+            if save:
+                qut, kt, qvt = [self._zeros(("dec", li, j, B, Tpad), (B * H, 64, Tpad), B16, dev, use_pool) for j in range(3)]
+            if T2:
+                call("sed_gemm_qkv_w2s", y16, W[pa + "in_proj.weight"].ws, self.P(pa + "in_proj.bias"), M, D, H, T, Tpad,
+                     qu, k, v, qut, kt, vt, qv, qvt, self.P(pa + "pos_bias_u"), self.P(pa + "pos_bias_v"), 3 if save else 1)
+            else:
+                call("sed_gemm_qkv", y16, wk(pa + "in_proj.weight"), self.P(pa + "in_proj.bias"), M, KD, H, T, Tpad,
+                     qu, k, v, qut, kt, vt, qv, qvt, self.P(pa + "pos_bias_u"), self.P(pa + "pos_bias_v"), 3 if (save and f16) else f16)
+            o16 = E(M, D, dt=F32 if SP else A16)
+            lse = E(B * H, T)
+            o16s = E(M, 3 * D, dt=F16) if SP else None
+            if hwt is None:
+                call("sed_relpos_attn_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0)
+            else:
+                call("sed_relpos_attn_band_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0, hwt)
+            x2 = E(M, D)
+            gemm_nt(o16s if SP else o16, wk(pa + "out_proj.weight"), EPI_F32_RESID, bias=self.P(pa + "out_proj.bias"), res=x1, outF=x2)
+            # ---- convolution module: x3 = x2 + pointwise_conv2(swish(norm(depthwise(glu(pointwise_conv1(norm_conv(x2)))))))
+            pc = p + "conv_module."
+            yc = img()
+            meanc, rstdc = (E(M), E(M)) if save else (None, None)
+            call("sed_layernorm_fwd", x2, self.P(p + "norm_conv.weight"), self.P(p + "norm_conv.bias"), 1e-5, 1.0, yc, None, meanc, rstdc,
+                 M, D, mode)
+            xp = E(M, 2 * D)
+            gemm_nt(yc, wk(pc + "pointwise_conv1.weight"), EPI_F32, bias=self.P(pc + "pointwise_conv1.bias"), outF=xp)
+            ys = img()
+            conv, cmean, crstd = (E(M, D), E(M), E(M)) if save else (None, None, None)
+            call("sed_conv_glu_dw_fwd", xp, self.P(pc + "depthwise_conv.weight"), self.P(pc + "depthwise_conv.bias"),
+                 self.P(pc + "norm.weight"), self.P(pc + "norm.bias"), 1e-5, ys, None, conv, cmean, crstd, B, T, D, mode)
+            x3 = E(M, D)
+            gemm_nt(ys, wk(pc + "pointwise_conv2.weight"), EPI_F32_RESID, bias=self.P(pc + "pointwise_conv2.bias"), res=x2, outF=x3)
+            x4, ff = self._swish_ffn_fwd(W, p + "feed_forward", p + "norm_ff", x3, M, save)
+            out = E(M, D)
+            fmean, frstd = (E(M), E(M)) if save else (None, None)
+            call("sed_layernorm_fwd", x4, self.P(p + "norm_final.weight"), self.P(p + "norm_final.bias"), 1e-5, 1.0, None, out, fmean, frstd,
+                 M, D, f16)
+            if save:
+                ctx["layers"].append(dict(ffm=ffm, ff=ff, x1=x1, y16=y16, mean1=mean1, rstd1=rstd1, Ph=Ph, Pt=Pt, qu=qu, qut=qut, qv=qv, qvt=qvt,
+                                          k=k, kt=kt, v=v, o16=o16, o16s=o16s, lse=lse, x2=x2, yc=yc, meanc=meanc, rstdc=rstdc, xp=xp, ys=ys,
+                                          conv=conv, cmean=cmean, crstd=crstd, x4=x4, fmean=fmean, frstd=frstd))
+            cur = out
+        return cur.view(B, T, D), ctx
+
     # ------------------------------------------------------------------ full forward
     def forward(self, mel, encoder_win=False, mix_rate=0.5, win_param=(512, 49), temp_w=1.0, pad_mask=None,
                 mlm_plan=None, toffsets=None, save=False):
@@ -769,7 +900,8 @@ class SedEngine:
                 call("sed_mlm_apply", xg, self.P("mask_token").reshape(D), mlm_plan["action"], mlm_plan["src_idx"],
                      dec_in, B * Tdec)
         # (heads-only training -- the finetune1 stage: nothing at or below the context network learns, its backward is never walked)
-        xd, dctx = self._decoder_fwd(W, dec_in, save and self._walks_decoder_fwd())
+        dec_fwd = self._conformer_fwd if m.decoder_name == "conformer" else self._decoder_fwd
+        xd, dctx = dec_fwd(W, dec_in, save and self._walks_decoder_fwd())
         actx = None
         if m.has_at:
             actx = self._at_fwd(W, frame16, ectx, save)
@@ -916,8 +1048,11 @@ class SedEngine:
                 hook("heads")
             return
         # ---------------- context network
-        dec_trainable = G("decoder.encoder_blocks.0.attn.in_proj.weight") is not None
-        g = self._decoder_bwd(W, ctx["dctx"], g, G, dec_trainable)
+        if m.decoder_name == "conformer":
+            g = self._conformer_bwd(W, ctx["dctx"], g, G, G("decoder.blocks.0.self_attn.in_proj.weight") is not None)
+        else:
+            dec_trainable = G("decoder.encoder_blocks.0.attn.in_proj.weight") is not None
+            g = self._decoder_bwd(W, ctx["dctx"], g, G, dec_trainable)
         # g = d(decoder input) [B, Tdec, D]
         if ctx["mlm_plan"] is not None:
             plan = ctx["mlm_plan"]
@@ -1256,6 +1391,100 @@ class SedEngine:
             g = gnew
             dctx["layers"][li] = None
         return g
+
+    def _swish_ffn_bwd(self, W, ff, norm, S, g2, M, Gl):
+        """Backward of `_swish_ffn_fwd`: adds d(xin) of the branch into the stream gradient g2 [M, D] fp32 (which already is the
+        gradient through the residual connection)."""
+        dev = g2.device
+        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        gh16 = E(M, D, dt=BF16)
+        call("sed_scale_add_f32", g2, None, None, gh16, M * D, 0.5)        # the branch enters the stream at 0.5
+        self._dw_accum(gh16, S["a"], M, Gl(ff + ".3.weight"), Gl(ff + ".3.bias"), k_in=D)
+        dact = E(M, D)
+        gemm_nt(gh16, W[ff + ".3.weight"].wt, EPI_F32, outF=dact)
+        dh16 = E(M, D, dt=BF16)
+        call("sed_swish_bwd", dact, S["h"], dh16, M * D)
+        self._dw_accum(dh16, S["y"], M, Gl(ff + ".0.weight"), Gl(ff + ".0.bias"), k_in=D)
+        gemm_nt(dh16, W[ff + ".0.weight"].wt, EPI_F32, outF=dact)
+        call("sed_layernorm_bwd", dact, S["x_in"], S["mean"], S["rstd"], self.P(norm + ".weight"), 1.0, g2, 1,
+             Gl(norm + ".weight"), Gl(norm + ".bias"), M, D)
+
+    def _conv_partials(self, B, T, dev):
+        """Scratch of sed_conv_glu_dw_bwd: one partial of every parameter gradient per workgroup (see include/sed_hip.h)."""
+        n = min(B * ((T + 19) // 20), 256) * 34 * D
+        t = getattr(self, "_conv_ws", None)
+        if t is None or t.numel() < n or t.device != dev:
+            t = self._conv_ws = torch.empty(n, dtype=F32, device=dev)
+        return t
+
+    def _conformer_bwd(self, W, dctx, g, G, trainable):
+        m = self.m
+        B, T, Tpad, Rpad = dctx["B"], dctx["T"], dctx["Tpad"], dctx["Rpad"]
+        M = B * T
+        dev = g.device
+        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        Z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
+        pos16, posT16, _ = self._pos(T, dev)
+        Gl = G if trainable else (lambda n: None)
+        g = g.contiguous()
+        for li in range(m.decoder_layer_num - 1, -1, -1):
+            p = f"decoder.blocks.{li}."
+            pa, pc = p + "self_attn.", p + "conv_module."
+            L = dctx["layers"][li]
+            g2 = E(M, D)
+            call("sed_layernorm_bwd", g.view(M, D), L["x4"], L["fmean"], L["frstd"], self.P(p + "norm_final.weight"), 1.0, g2, 0,
+                 Gl(p + "norm_final.weight"), Gl(p + "norm_final.bias"), M, D)
+            self._swish_ffn_bwd(W, p + "feed_forward", p + "norm_ff", L["ff"], g2, M, Gl)
+            # ---- convolution module
+            wv = lambda n: None if Gl(n) is None else Gl(n).view(W[n].w.shape)         # Conv1d [out, in, 1] gradient as the [out, in] matrix
+            g16 = self._dw_accum(g2, L["ys"], M, wv(pc + "pointwise_conv2.weight"), Gl(pc + "pointwise_conv2.bias"), k_in=D)
+            dys = E(M, D)
+            gemm_nt(g16, W[pc + "pointwise_conv2.weight"].wt, EPI_F32, outF=dys)
+            dxp = E(M, 2 * D, dt=BF16)
+            call("sed_conv_glu_dw_bwd", dys, L["xp"], L["conv"], L["cmean"], L["crstd"], self.P(pc + "depthwise_conv.weight"),
+                 self.P(pc + "norm.weight"), self.P(pc + "norm.bias"), dxp, Gl(pc + "depthwise_conv.weight"), Gl(pc + "depthwise_conv.bias"),
+                 Gl(pc + "norm.weight"), Gl(pc + "norm.bias"), self._conv_partials(B, T, dev), self._conv_partials(B, T, dev).numel(), B, T, D)
+            self._dw_accum(dxp, L["yc"], M, wv(pc + "pointwise_conv1.weight"), Gl(pc + "pointwise_conv1.bias"), k_in=D)
+            gemm_nt(dxp, W[pc + "pointwise_conv1.weight"].wt, EPI_F32, outF=dys)
+            call("sed_layernorm_bwd", dys, L["x2"], L["meanc"], L["rstdc"], self.P(p + "norm_conv.weight"), 1.0, g2, 1,
+                 Gl(p + "norm_conv.weight"), Gl(p + "norm_conv.bias"), M, D)
+            del dys, dxp
+            # ---- attention
+            g16 = self._dw_accum(g2, L["o16s"] if L.get("o16s") is not None else L["o16"], M, Gl(pa + "out_proj.weight"),
+                                 Gl(pa + "out_proj.bias"), k_in=D)
+            do16 = E(M, D, dt=BF16)
+            gemm_nt(g16, W[pa + "out_proj.weight"].wt, EPI_BF16, outH=do16)
+            dqkv = E(M, 3 * D, dt=BF16)
+            Dtmp = E(B * H, T)
+            dOh = E(B * H, T, 64, dt=BF16)
+            dOt = E(B * H, 64, Tpad, dt=BF16)
+            dSt = self._zeros(("dSt", B, Tpad), (B * H, Tpad, Tpad), BF16, dev)
+            Pst = self._zeros(("Pst", B, Tpad), (B * H, Tpad, Tpad), BF16, dev) if self.relpos_stream else None
+            dP = Z(Rpad, D)
+            du, dv = Gl(pa + "pos_bias_u"), Gl(pa + "pos_bias_v")
+            scratch_uv = Z(2, D)
+            f16 = is_f16(L["qu"])
+            hwt = band_half_width(m, dev, T)
+            call("sed_relpos_attn_bwd" if hwt is None else "sed_relpos_attn_band_bwd", L["qu"], to_bf16_(L["qut"]), L["qv"],
+                 to_bf16_(L["qvt"]), L["k"], to_bf16_(L["kt"]), to_bf16_(L["v"]), L["Ph"], to_bf16_(L["Pt"]), L["o16"], do16, L["lse"],
+                 Dtmp, dOh, dOt, dqkv, dSt, Pst, dP, du if du is not None else scratch_uv[0], dv if dv is not None else scratch_uv[1],
+                 B, H, T, Tpad, Rpad, 1 if trainable else 0, f16, o_kind(L["o16"]), *(() if hwt is None else (hwt,)))
+            del dSt, Pst, dOh, dOt, do16
+            if trainable:
+                dPT = E(D, Rpad, dt=BF16)
+                transpose_bf16(dP, Rpad, D, dPT)
+                gemm_dw(dPT, posT16, G(pa + "linear_pos.weight"))
+                self._dw_accum(dqkv, L["y16"], M, G(pa + "in_proj.weight"), G(pa + "in_proj.bias"), k_in=D)
+            dln = E(M, D)
+            gemm_nt(dqkv, W[pa + "in_proj.weight"].wt, EPI_F32, outF=dln)
+            call("sed_layernorm_bwd", dln, L["x1"], L["mean1"], L["rstd1"], self.P(p + "norm_mha.weight"), 1.0, g2, 1,
+                 Gl(p + "norm_mha.weight"), Gl(p + "norm_mha.bias"), M, D)
+            del dln, dqkv
+            self._swish_ffn_bwd(W, p + "feed_forward_macaron", p + "norm_ff_macaron", L["ffm"], g2, M, Gl)
+            g = g2
+            dctx["layers"][li] = None
+        call("sed_scale_add_f32", g, None, g, None, M * D, math.sqrt(D))       # the stream started as sqrt(D) x
+        return g.view(B, T, D)
 
     def _at_bwd(self, W, a, ectx, dat, G, need_dx):
         """Backward of the AT head.  Returns d(encoder residual stream) [B, N, D] (or None when not needed)."""

@@ -199,6 +199,51 @@ class _Decoder(_Holder):
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
 
+class _ConvModule(_Holder):
+    """Parameter layout of `ConvolutionModule` (src/models/transformer/conformer.py:155-213); the convolutions keep their Conv1d shapes
+    ([out, in, 1], [channels, 1, 31]) and torch's default initialisation."""
+
+    def __init__(self, dim, kernel_size=31):
+        super().__init__()
+        self.pointwise_conv1 = nn.Conv1d(dim, 2 * dim, kernel_size=1)
+        self.depthwise_conv = nn.Conv1d(dim, dim, kernel_size, padding=(kernel_size - 1) // 2, groups=dim)
+        self.norm = nn.LayerNorm(dim)
+        self.pointwise_conv2 = nn.Conv1d(dim, dim, kernel_size=1)
+
+
+class _Identity(nn.Module):
+    """Parameter-free placeholder that keeps the reference's nn.Sequential indices (Swish at 1, Dropout at 2)."""
+
+
+class _ConformerBlock(_Holder):
+    """Parameter layout of `ConformerEncoderLayer` (conformer.py:32-73), in the reference's registration order."""
+
+    def __init__(self, dim, heads):
+        super().__init__()
+        self.self_attn = _RelAttn(dim, heads)
+        self.feed_forward = nn.Sequential(nn.Linear(dim, dim), _Identity(), _Identity(), nn.Linear(dim, dim))
+        self.feed_forward_macaron = nn.Sequential(nn.Linear(dim, dim), _Identity(), _Identity(), nn.Linear(dim, dim))
+        self.conv_module = _ConvModule(dim)
+        self.norm_ff_macaron = nn.LayerNorm(dim)
+        self.norm_ff = nn.LayerNorm(dim)
+        self.norm_mha = nn.LayerNorm(dim)
+        self.norm_conv = nn.LayerNorm(dim)
+        self.norm_final = nn.LayerNorm(dim)
+
+
+class _ConformerDecoder(_Decoder):
+    """Parameter layout of `ConformerDecoder` (src/models/transformer_decoder.py:125-155): `blocks` instead of `encoder_blocks`, the same
+    `att_mask` buffer.  The reference hands `window_len` straight to `diagonal_mask`, which takes ONE width: a sequence is refused."""
+
+    def __init__(self, dim, layers, heads, seq_len=1000, win_len=None):
+        if win_len is not None and (isinstance(win_len, bool) or not isinstance(win_len, int)):
+            raise TypeError("decoder_win_len of the conformer decoder must be one int or None (the reference passes it to diagonal_mask, "
+                            f"which takes a single width; per-head windows exist for decoder='transformerXL' only), got {win_len!r}")
+        super().__init__(dim, 0, heads, seq_len=seq_len, win_len=win_len)
+        del self.encoder_blocks
+        self.blocks = nn.ModuleList([_ConformerBlock(dim, heads) for _ in range(layers)])
+
+
 class _AttnPool(_Holder):
     def __init__(self, dim, heads):
         super().__init__()
@@ -292,7 +337,8 @@ class PaSST_SED(SEDModel):
             if embed_dim != D or decoder_dim != D: unsupported.append("embed_dim/decoder_dim != 768")
             if f_pool != "mean_pool": unsupported.append(f"f_pool={f_pool!r}")
             if lora_config is not None: unsupported.append("LoRA")
-        if decoder != "transformerXL": unsupported.append(f"decoder={decoder!r}")
+        if decoder not in (("transformerXL",) if _pmam else ("transformerXL", "conformer")):
+            unsupported.append(f"decoder={decoder!r}" + (" (the conformer decoder exists for PaSST_SED only)" if decoder == "conformer" else ""))
         if s_patchout_f or s_patchout_t: unsupported.append("patchout")
         if interpolate_mode != "linear": unsupported.append(f"interpolate_mode={interpolate_mode!r}")
         if unsupported:
@@ -337,7 +383,8 @@ class PaSST_SED(SEDModel):
             if mlm_dict["out_dim"] != D:
                 raise NotImplementedError("mlm out_dim != 768")
         self.decoder_layer_num = decoder_layer_num
-        self.decoder = _Decoder(decoder_dim, decoder_layer_num, H, seq_len=decoder_pos_emd_len, win_len=decoder_win_len)
+        self.decoder = (_ConformerDecoder if decoder == "conformer" else _Decoder)(decoder_dim, decoder_layer_num, H, seq_len=decoder_pos_emd_len,
+                                                                                     win_len=decoder_win_len)
         self.classifier = nn.Linear(decoder_dim, class_num)
         self.has_at = bool(at_adapter)
         self.at_adpater = at_adapter  # (sic) spelling is part of the checkpoint contract

@@ -147,6 +147,62 @@ def matsed_state_dict_np(tag="w0", **kw):
 
 
 # --------------------------------------------------------------------------------------------------
+# MAT-SED with the Conformer context network, PaSST_SED(decoder="conformer") (reference definition sites:
+# src/models/transformer_decoder.py:125-155, src/models/transformer/conformer.py:32-73,166-213)
+# --------------------------------------------------------------------------------------------------
+def conformer_block_shapes(prefix, D=768, n_heads=12, kernel_size=31):
+    p, s = prefix, {}
+    s[p + "self_attn.pos_bias_u"] = (n_heads, D // n_heads)
+    s[p + "self_attn.pos_bias_v"] = (n_heads, D // n_heads)
+    s[p + "self_attn.in_proj.weight"] = (3 * D, D)
+    s[p + "self_attn.in_proj.bias"] = (3 * D,)
+    s[p + "self_attn.out_proj.weight"] = (D, D)
+    s[p + "self_attn.out_proj.bias"] = (D,)
+    s[p + "self_attn.linear_pos.weight"] = (D, D)
+    for ff in ("feed_forward", "feed_forward_macaron"):
+        for i in (0, 3):
+            s[p + f"{ff}.{i}.weight"] = (D, D)
+            s[p + f"{ff}.{i}.bias"] = (D,)
+    s[p + "conv_module.pointwise_conv1.weight"] = (2 * D, D, 1)
+    s[p + "conv_module.pointwise_conv1.bias"] = (2 * D,)
+    s[p + "conv_module.depthwise_conv.weight"] = (D, 1, kernel_size)
+    s[p + "conv_module.depthwise_conv.bias"] = (D,)
+    s[p + "conv_module.norm.weight"] = (D,)
+    s[p + "conv_module.norm.bias"] = (D,)
+    s[p + "conv_module.pointwise_conv2.weight"] = (D, D, 1)
+    s[p + "conv_module.pointwise_conv2.bias"] = (D,)
+    for n in ("norm_ff_macaron", "norm_ff", "norm_mha", "norm_conv", "norm_final"):
+        s[p + n + ".weight"] = (D,)
+        s[p + n + ".bias"] = (D,)
+    return s
+
+
+def conformer_state_dict_np(tag="wc0", dec_layers=2, tap_scale=0.35, **kw):
+    """`matsed_state_dict_np` with the context network replaced by `dec_layers` Conformer blocks under `decoder.blocks.{i}.` (66 tensors
+    at two layers).  LayerNorm weights near 1, linear / pointwise weights at unit gain; the depthwise taps are uniform in +-tap_scale, so
+    that the 30 off-centre taps carry most of the convolution's output (tools/gen_conformer_golden.py asserts that the posteriors move by
+    >= 20e-3 when they are cut)."""
+    D = kw.get("embed_dim", 768)
+    out = matsed_state_dict_np(tag=tag, dec_layers=0, **kw)
+    for i in range(dec_layers):
+        for name, shp in conformer_block_shapes(f"decoder.blocks.{i}.", D, kw.get("n_heads", 12)).items():
+            key = f"{tag}/{name}"
+            if name.endswith("depthwise_conv.weight"):
+                w = tap_scale * det_uniform(key, shp)
+            elif name.endswith(".bias"):
+                w = 0.1 * det_uniform(key, shp)
+            elif "norm" in name:
+                w = 1.0 + 0.2 * det_uniform(key, shp)
+            elif "pos_bias_" in name:
+                w = 0.5 * det_uniform(key, shp)
+            else:       # linear [out, in] and 1-tap convolution [out, in, 1] weights
+                gain = 1.6 if ("in_proj" in name or "linear_pos" in name) else 1.0
+                w = det_uniform(key, shp) * (gain * math.sqrt(3.0 / shp[1]))
+            out[name] = w.astype(np.float32)
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # PMAM `PaSST_CNN` state_dict (SURVEY.md section 8(f) rank 3; reference definition sites:
 # src/models/cnn_transformer/passt_cnn.py:11-20, src/models/cnn/base.py:62-98, src/models/lora/layers.py:107-116,
 # src/models/passt/passt_lora.py:116-125, src/models/pooling.py:39-43; values of config/pmam/post_pretrain.yaml:47-80)
