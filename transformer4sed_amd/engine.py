@@ -87,6 +87,22 @@ def rel_pos_table(T, Dm=D):
     return torch.cat([torch.flip(pp, [0]), pn[1:]], dim=0)
 
 
+def in_split_precision(fwd):
+    """Decorator of a context-network forward: every GEMM of it runs on split-precision operands (3x K issued), so the whole call runs
+    inside ops.split_precision(), entered once.  An engine without `split` does not enter it."""
+    def run(self, *args):
+        if not self.split or getattr(self, "_in_split", False):
+            return fwd(self, *args)
+        self._in_split = True
+        try:
+            with ops.split_precision():
+                return fwd(self, *args)
+        finally:
+            self._in_split = False
+    run.__doc__ = fwd.__doc__
+    return run
+
+
 class _W:
     """bf16 operand images of one fp32 weight matrix [n_out, k_in] (rewritten by every forward), and the images cached across forwards
     (`cached_image`): LayerNorm-folded `lnf`, two-term `w2` (f16 or fp8 form), residual `wlo`, each beside its key."""
@@ -614,79 +630,95 @@ class SedEngine:
         return pooled
 
     # ------------------------------------------------------------------ context network
+    def _relattn_terms2(self, M):
+        """in_proj on two split-precision terms and linear_pos on plain operands (see `dec_terms2`; the 256^2 kernel's domain).  Decides the
+        image the LayerNorm in front of `_relattn_fwd` writes, the table `_pos` hands out and the qkv entry point."""
+        return self.split and self.dec_terms2 and M >= 1024
+
+    def _relattn_fwd(self, W, pa, li, ctx, pos16, hwt, yop, res, bias, save):
+        """res + out_proj(relattn(y)): the rel-pos attention sub-block of every context network (Transformer-XL, Conformer, PMAM's 384-wide
+        one).  `pa`: parameter prefix of in_proj / linear_pos / out_proj; `ctx`: B / T / Tpad / Rpad of this forward; `hwt`: the local
+        window (`band_half_width`) or None; `yop`: operand image of the normalised input y -- plain f16 under `_relattn_terms2`, else
+        [hi | lo | hi] in split precision; `res` fp32: what out_proj adds to, its last dim is the model width; `bias`: (in_proj bias,
+        pos_bias_u, pos_bias_v) as the qkv kernel reads them.  The attention is H * 64 wide whatever the model width (a narrower model
+        passes padded-head weight images).  Returns the new stream (shaped like `res`) and the tensors `_relattn_bwd` reads."""
+        B, T, Tpad, Rpad = ctx["B"], ctx["T"], ctx["Tpad"], ctx["Rpad"]
+        M, Dm, Da = B * T, res.shape[-1], H * 64
+        dev = res.device
+        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        A16 = self.act
+        f16 = 1 if A16 == F16 else 0
+        SP = self.split
+        T2 = self._relattn_terms2(M)
+        wk = (lambda n: W[pa + n].ws) if SP else (lambda n: W[pa + n].w)   # forward operand image of a weight
+        # p = linear_pos(pos_emb), head-split [H, Rpad, 64] (+ transposed [H, 64, Rpad] for backward)
+        Ph = E(H, Rpad, 64, dt=A16)
+        Pt = torch.zeros(H, 64, Rpad, dtype=A16, device=dev) if save else None
+        ptmp = E(Rpad, Da, dt=A16)
+        if T2:
+            with ops.plain_precision():
+                gemm_nt(pos16, W[pa + "linear_pos.weight"].w, EPI_BF16, outH=ptmp)
+        else:
+            gemm_nt(pos16, wk("linear_pos.weight"), EPI_BF16, outH=ptmp)
+        Ph.copy_(ptmp.view(Rpad, H, 64).permute(1, 0, 2))
+        if save:
+            Pt.copy_(ptmp.view(Rpad, H, 64).permute(1, 2, 0))
+        B16 = BF16 if save else A16   # backward-only tensors (row-major V, transposed q+u / q+v / K)
+        qu, k = [E(B * H, T, 64, dt=A16) for _ in range(2)]
+        v = E(B * H, T, 64, dt=B16)
+        qv = E(B * H, T, 64, dt=A16)
+        use_pool = getattr(self, "_lease_ok", False) or not save
+        vt = self._zeros(("dec_vt", li, B, Tpad), (B * H, 64, Tpad), A16, dev, use_pool)
+        qut = kt = qvt = None
+        if save:
+            qut, kt, qvt = [self._zeros(("dec", li, j, B, Tpad), (B * H, 64, Tpad), B16, dev, use_pool) for j in range(3)]
+        if T2:
+            call("sed_gemm_qkv_w2s", yop, W[pa + "in_proj.weight"].ws, bias[0], M, Dm, H, T, Tpad,
+                 qu, k, v, qut, kt, vt, qv, qvt, bias[1], bias[2], 3 if save else 1)
+        else:
+            call("sed_gemm_qkv", yop, wk("in_proj.weight"), bias[0], M, 3 * Dm if SP else Dm, H, T, Tpad,
+                 qu, k, v, qut, kt, vt, qv, qvt, bias[1], bias[2], 3 if (save and f16) else f16)
+        o16 = E(M, Da, dt=F32 if SP else A16)
+        lse = E(B * H, T)
+        o16s = E(M, 3 * Da, dt=F16) if SP else None      # split-precision image of the attention output, written by the kernel itself
+        if hwt is None:
+            call("sed_relpos_attn_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0)
+        else:       # local window (decoder_win_len): the band kernels skip the key tiles no query of a workgroup sees
+            call("sed_relpos_attn_band_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0, hwt)
+        out = E(*res.shape)
+        gemm_nt(o16s if SP else o16, wk("out_proj.weight"), EPI_F32_RESID, bias=self.P(pa + "out_proj.bias"), res=res, outF=out)
+        # (split precision: y16 / o16s are [M, 3 K] images whose first third is the f16 operand of the weight gradients)
+        return out, (dict(y16=yop, Ph=Ph, Pt=Pt, qu=qu, qut=qut, qv=qv, qvt=qvt, k=k, kt=kt, v=v, o16=o16, o16s=o16s, lse=lse) if save else None)
+
+    @in_split_precision
     def _decoder_fwd(self, W, x, save):
         """TransformerXLDecoder (src/models/transformer_decoder.py:110-122, transformerXL.py:31-35). x [B,T,D] f32."""
         m = self.m
         dev = x.device
         B, T, _ = x.shape
-        Tpad = pad64(T)
         M = B * T
-        pos16, posT16, Rpad = self._pos(T, dev, want_plain=M >= 1024)
+        T2 = self._relattn_terms2(M)
+        pos16, _, Rpad = self._pos(T, dev, want_plain=T2)
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         A16 = self.act
         f16 = 1 if A16 == F16 else 0
-        ctx = dict(B=B, T=T, Tpad=Tpad, Rpad=Rpad, layers=[])
+        ctx = dict(B=B, T=T, Tpad=pad64(T), Rpad=Rpad, layers=[])
         cur = x
         SP = self.split
-        if SP and not getattr(self, "_in_split", False):   # every GEMM of this forward runs on split-precision operands (3x K issued)
-            self._in_split = True
-            try:
-                with ops.split_precision():
-                    return self._decoder_fwd(W, x, save)
-            finally:
-                self._in_split = False
         hwt = band_half_width(m, dev, T)
         for li in range(m.decoder_layer_num):
             p = f"decoder.encoder_blocks.{li}."
+            pa = p + "attn."
             in_scale = math.sqrt(D) if li == 0 else 1.0
             wk = (lambda n: W[n].ws) if SP else (lambda n: W[n].w)   # forward operand image of a decoder weight
-            KD = 3 * D if SP else D
-            T2 = SP and self.dec_terms2 and M >= 1024       # in_proj / linear_pos on fewer terms (see `dec_terms2`; the 256^2 kernel's domain)
             # split precision: the LayerNorm writes the [hi | lo | hi] image itself (two-term in_proj: the plain f16 image is all it reads)
             y16 = E(M, 3 * D, dt=F16) if (SP and not T2) else E(M, D, dt=A16)
             y32 = E(B, T, D)
             mean1, rstd1 = (E(M), E(M)) if save else (None, None)
             call("sed_layernorm_fwd", cur, self.P(p + "norm1.weight"), self.P(p + "norm1.bias"), 1e-5, in_scale, y16,
                  y32, mean1, rstd1, M, D, 4 if (SP and not T2) else f16)
-            yop = y16
-            # p = linear_pos(pos_emb), head-split [H, Rpad, 64] (+ transposed [H, 64, Rpad] for backward)
-            Ph = E(H, Rpad, 64, dt=A16)
-            Pt = torch.zeros(H, 64, Rpad, dtype=A16, device=dev) if save else None
-            ptmp = E(Rpad, D, dt=A16)
-            if T2:
-                with ops.plain_precision():
-                    gemm_nt(pos16, W[p + "attn.linear_pos.weight"].w, EPI_BF16, outH=ptmp)
-            else:
-                gemm_nt(pos16, wk(p + "attn.linear_pos.weight"), EPI_BF16, outH=ptmp)
-            Ph.copy_(ptmp.view(Rpad, H, 64).permute(1, 0, 2))
-            if save:
-                Pt.copy_(ptmp.view(Rpad, H, 64).permute(1, 2, 0))
-            B16 = BF16 if save else A16   # backward-only tensors (row-major V, transposed q+u / q+v / K, pre-activations)
-            qu, k = [E(B * H, T, 64, dt=A16) for _ in range(2)]
-            v = E(B * H, T, 64, dt=B16)
-            qv = E(B * H, T, 64, dt=A16)
-            use_pool = getattr(self, "_lease_ok", False) or not save
-            vt = self._zeros(("dec_vt", li, B, Tpad), (B * H, 64, Tpad), A16, dev, use_pool)
-            qut = kt = qvt = None
-            if save:
-                qut, kt, qvt = [self._zeros(("dec", li, j, B, Tpad), (B * H, 64, Tpad), B16, dev, use_pool) for j in range(3)]
-            if T2:
-                call("sed_gemm_qkv_w2s", yop, W[p + "attn.in_proj.weight"].ws, self.P(p + "attn.in_proj.bias"), M, D, H, T, Tpad,
-                     qu, k, v, qut, kt, vt, qv, qvt, self.P(p + "attn.pos_bias_u"), self.P(p + "attn.pos_bias_v"), 3 if save else 1)
-            else:
-                call("sed_gemm_qkv", yop, wk(p + "attn.in_proj.weight"), self.P(p + "attn.in_proj.bias"), M, KD, H, T, Tpad,
-                     qu, k, v, qut, kt, vt, qv, qvt, self.P(p + "attn.pos_bias_u"), self.P(p + "attn.pos_bias_v"),
-                     3 if (save and f16) else f16)
-            o16 = E(M, D, dt=F32 if SP else A16)
-            lse = E(B * H, T)
-            o16s = E(M, 3 * D, dt=F16) if SP else None      # split-precision image of the attention output, written by the kernel itself
-            if hwt is None:
-                call("sed_relpos_attn_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0)
-            else:       # local window (decoder_win_len): the band kernels skip the key tiles no query of a workgroup sees
-                call("sed_relpos_attn_band_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0, hwt)
-            x1 = E(B, T, D)
-            gemm_nt(o16s if SP else o16, wk(p + "attn.out_proj.weight"), EPI_F32_RESID,
-                    bias=self.P(p + "attn.out_proj.bias"), res=y32, outF=x1)
+            x1, att = self._relattn_fwd(W, pa, li, ctx, pos16, hwt, y16, y32,
+                                        (self.P(pa + "in_proj.bias"), self.P(pa + "pos_bias_u"), self.P(pa + "pos_bias_v")), save)
             h2 = E(M, D, dt=F32 if SP else A16)
             h2s = E(M, 3 * D, dt=F16) if SP else None
             mean2, rstd2 = (E(M), E(M)) if save else (None, None)
@@ -696,7 +728,7 @@ class SedEngine:
                  h2s if SP else h2, None, mean2, rstd2, M, D, 4 if SP else f16)
             if SP:
                 h2 = h2s
-            hpre = E(M, D, dt=B16)
+            hpre = E(M, D, dt=BF16 if save else A16)      # (read by the backward only)
             if SP:
                 act = E(M, D)
                 gemm_nt(h2s, wk(p + "mlp.fc1.weight"), EPI_GELU32, bias=self.P(p + "mlp.fc1.bias"), outH=hpre,
@@ -710,10 +742,9 @@ class SedEngine:
             gemm_nt(act, wk(p + "mlp.fc2.weight"), EPI_F32_RESID,
                     bias=self.P(p + "mlp.fc2.bias"), res=x1, outF=x2)
             if save:
-                # split precision: y16 / h2 / act / o16s are [M, 3 D] images whose first third is the f16 operand of the weight gradients
-                ctx["layers"].append(dict(x_in=cur, in_scale=in_scale, y16=y16, mean1=mean1,
-                                          rstd1=rstd1, Ph=Ph, Pt=Pt, qu=qu, qut=qut, qv=qv, qvt=qvt, k=k, kt=kt, v=v,
-                                          o16=o16, o16s=o16s, lse=lse, x1=x1, h2=h2, mean2=mean2, rstd2=rstd2, hpre=hpre, act=act))
+                # split precision: h2 / act are [M, 3 D] images whose first third is the f16 operand of the weight gradients
+                ctx["layers"].append(dict(att, x_in=cur, in_scale=in_scale, mean1=mean1, rstd1=rstd1, x1=x1, h2=h2, mean2=mean2,
+                                          rstd2=rstd2, hpre=hpre, act=act))
             cur = x2
         return cur, ctx
 
@@ -739,6 +770,7 @@ class SedEngine:
         call("sed_scale_add_f32", out, xin, out, None, M * D, 0.5)
         return out, (dict(x_in=xin, y=y, mean=mean, rstd=rstd, h=h, a=a) if save else None)
 
+    @in_split_precision
     def _conformer_fwd(self, W, x, save):
         """ConformerDecoder (src/models/transformer_decoder.py:157-165, conformer.py:75-144).  x [B,T,D] f32.  Per block, on the residual
         stream s (which starts as sqrt(D) x: RelPositionalEncoding's scaling is applied to the stream itself here):
@@ -748,25 +780,17 @@ class SedEngine:
         m = self.m
         dev = x.device
         B, T, _ = x.shape
-        Tpad = pad64(T)
         M = B * T
         SP = self.split
-        if SP and not getattr(self, "_in_split", False):
-            self._in_split = True
-            try:
-                with ops.split_precision():
-                    return self._conformer_fwd(W, x, save)
-            finally:
-                self._in_split = False
-        pos16, posT16, Rpad = self._pos(T, dev, want_plain=M >= 1024)
+        T2 = self._relattn_terms2(M)
+        pos16, _, Rpad = self._pos(T, dev, want_plain=T2)
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         A16 = self.act
         f16 = 1 if A16 == F16 else 0
         mode = 4 if SP else f16
         img = lambda: E(M, 3 * D, dt=F16) if SP else E(M, D, dt=A16)
         wk = (lambda n: W[n].ws) if SP else (lambda n: W[n].w)
-        KD = 3 * D if SP else D
-        ctx = dict(B=B, T=T, Tpad=Tpad, Rpad=Rpad, layers=[])
+        ctx = dict(B=B, T=T, Tpad=pad64(T), Rpad=Rpad, layers=[])
         hwt = band_half_width(m, dev, T)
         cur = E(M, D)
         call("sed_scale_add_f32", x, None, cur, None, M * D, math.sqrt(D))
@@ -775,46 +799,12 @@ class SedEngine:
             pa = p + "self_attn."
             x1, ffm = self._swish_ffn_fwd(W, p + "feed_forward_macaron", p + "norm_ff_macaron", cur, M, save)
             # ---- attention: x2 = x1 + out_proj(relattn(norm_mha(x1)))
-            T2 = SP and self.dec_terms2 and M >= 1024
             y16 = E(M, 3 * D, dt=F16) if (SP and not T2) else E(M, D, dt=A16)
             mean1, rstd1 = (E(M), E(M)) if save else (None, None)
             call("sed_layernorm_fwd", x1, self.P(p + "norm_mha.weight"), self.P(p + "norm_mha.bias"), 1e-5, 1.0, y16, None, mean1, rstd1,
                  M, D, 4 if (SP and not T2) else f16)
-            Ph = E(H, Rpad, 64, dt=A16)
-            Pt = torch.zeros(H, 64, Rpad, dtype=A16, device=dev) if save else None
-            ptmp = E(Rpad, D, dt=A16)
-            if T2:
-                with ops.plain_precision():
-                    gemm_nt(pos16, W[pa + "linear_pos.weight"].w, EPI_BF16, outH=ptmp)
-            else:
-                gemm_nt(pos16, wk(pa + "linear_pos.weight"), EPI_BF16, outH=ptmp)
-            Ph.copy_(ptmp.view(Rpad, H, 64).permute(1, 0, 2))
-            if save:
-                Pt.copy_(ptmp.view(Rpad, H, 64).permute(1, 2, 0))
-            B16 = BF16 if save else A16
-            qu, k = [E(B * H, T, 64, dt=A16) for _ in range(2)]
-            v = E(B * H, T, 64, dt=B16)
-            qv = E(B * H, T, 64, dt=A16)
-            use_pool = getattr(self, "_lease_ok", False) or not save
-            vt = self._zeros(("dec_vt", li, B, Tpad), (B * H, 64, Tpad), A16, dev, use_pool)
-            qut = kt = qvt = None
-            if save:
-                qut, kt, qvt = [self._zeros(("dec", li, j, B, Tpad), (B * H, 64, Tpad), B16, dev, use_pool) for j in range(3)]
-            if T2:
-                call("sed_gemm_qkv_w2s", y16, W[pa + "in_proj.weight"].ws, self.P(pa + "in_proj.bias"), M, D, H, T, Tpad,
-                     qu, k, v, qut, kt, vt, qv, qvt, self.P(pa + "pos_bias_u"), self.P(pa + "pos_bias_v"), 3 if save else 1)
-            else:
-                call("sed_gemm_qkv", y16, wk(pa + "in_proj.weight"), self.P(pa + "in_proj.bias"), M, KD, H, T, Tpad,
-                     qu, k, v, qut, kt, vt, qv, qvt, self.P(pa + "pos_bias_u"), self.P(pa + "pos_bias_v"), 3 if (save and f16) else f16)
-            o16 = E(M, D, dt=F32 if SP else A16)
-            lse = E(B * H, T)
-            o16s = E(M, 3 * D, dt=F16) if SP else None
-            if hwt is None:
-                call("sed_relpos_attn_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0)
-            else:
-                call("sed_relpos_attn_band_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0, hwt)
-            x2 = E(M, D)
-            gemm_nt(o16s if SP else o16, wk(pa + "out_proj.weight"), EPI_F32_RESID, bias=self.P(pa + "out_proj.bias"), res=x1, outF=x2)
+            x2, att = self._relattn_fwd(W, pa, li, ctx, pos16, hwt, y16, x1,
+                                        (self.P(pa + "in_proj.bias"), self.P(pa + "pos_bias_u"), self.P(pa + "pos_bias_v")), save)
             # ---- convolution module: x3 = x2 + pointwise_conv2(swish(norm(depthwise(glu(pointwise_conv1(norm_conv(x2)))))))
             pc = p + "conv_module."
             yc = img()
@@ -835,9 +825,8 @@ class SedEngine:
             call("sed_layernorm_fwd", x4, self.P(p + "norm_final.weight"), self.P(p + "norm_final.bias"), 1e-5, 1.0, None, out, fmean, frstd,
                  M, D, f16)
             if save:
-                ctx["layers"].append(dict(ffm=ffm, ff=ff, x1=x1, y16=y16, mean1=mean1, rstd1=rstd1, Ph=Ph, Pt=Pt, qu=qu, qut=qut, qv=qv, qvt=qvt,
-                                          k=k, kt=kt, v=v, o16=o16, o16s=o16s, lse=lse, x2=x2, yc=yc, meanc=meanc, rstdc=rstdc, xp=xp, ys=ys,
-                                          conv=conv, cmean=cmean, crstd=crstd, x4=x4, fmean=fmean, frstd=frstd))
+                ctx["layers"].append(dict(att, ffm=ffm, ff=ff, x1=x1, mean1=mean1, rstd1=rstd1, x2=x2, yc=yc, meanc=meanc, rstdc=rstdc, xp=xp,
+                                          ys=ys, conv=conv, cmean=cmean, crstd=crstd, x4=x4, fmean=fmean, frstd=frstd))
             cur = out
         return cur.view(B, T, D), ctx
 
@@ -1333,20 +1322,69 @@ class SedEngine:
         ectx["layers"][li] = None  # free saved activations
         return g
 
+    def _relattn_sink(self, Gl, pa, dev):
+        """Where `_relattn_bwd` adds the parameter gradients of the attention at prefix `pa`, as arena views: (weight, bias) of out_proj
+        and in_proj, linear_pos's weight, pos_bias_u / v.  `Gl` names nothing in a frozen context network; the kernel still writes
+        du / dv somewhere."""
+        scratch_uv = torch.zeros(2, D, dtype=F32, device=dev)
+        du, dv = Gl(pa + "pos_bias_u"), Gl(pa + "pos_bias_v")
+        return dict(out_proj=(Gl(pa + "out_proj.weight"), Gl(pa + "out_proj.bias")), linear_pos=Gl(pa + "linear_pos.weight"),
+                    in_proj=(Gl(pa + "in_proj.weight"), Gl(pa + "in_proj.bias")),
+                    pos_bias_u=du if du is not None else scratch_uv[0], pos_bias_v=dv if dv is not None else scratch_uv[1])
+
+    def _relattn_bwd(self, W, pa, L, dctx, posT16, hwt, g2, sink, out_k_in, residual):
+        """Backward of `_relattn_fwd` given the stream gradient g2 [M, model width] fp32 and the forward's saved tensors `L`.  `sink`: the
+        gradient destinations by role (see `_relattn_sink`; linear_pos None = frozen: only the input gradient is computed); `out_k_in`:
+        `k_in` of out_proj's `_dw_accum`.  The gradient at the normalised input is added into `residual` (fp32 [M, model width]) when
+        given, else returned in a new tensor."""
+        B, T, Tpad, Rpad = dctx["B"], dctx["T"], dctx["Tpad"], dctx["Rpad"]
+        M, Dm, Da = B * T, g2.shape[1], H * 64
+        dev = g2.device
+        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        train = sink["linear_pos"] is not None
+        g16 = self._dw_accum(g2, L["o16s"] if L.get("o16s") is not None else L["o16"], M, *sink["out_proj"], k_in=out_k_in)
+        do16 = E(M, Da, dt=BF16)
+        gemm_nt(g16, W[pa + "out_proj.weight"].wt, EPI_BF16, outH=do16)
+        dqkv = E(M, 3 * Da, dt=BF16)
+        Dtmp = E(B * H, T)
+        dOh = E(B * H, T, 64, dt=BF16)
+        dOt = E(B * H, 64, Tpad, dt=BF16)
+        dSt = self._zeros(("dSt", B, Tpad), (B * H, Tpad, Tpad), BF16, dev)      # scratch of this call: one buffer for all layers
+        # P^T slab beside it: dK / dV as contractions over the two stored slabs (SED_RELPOS_DKDV=recompute: the score-recomputing kernel)
+        Pst = self._zeros(("Pst", B, Tpad), (B * H, Tpad, Tpad), BF16, dev) if self.relpos_stream else None
+        dP = torch.zeros(Rpad, Da, dtype=F32, device=dev)
+        # (local window: the pooled slabs may hold the full-window content of an earlier call outside the band -- the band kernels
+        #  neither write nor read those tiles, see relpos_attention.hip band_tile_lo / band_tile_hi)
+        call("sed_relpos_attn_bwd" if hwt is None else "sed_relpos_attn_band_bwd", L["qu"], to_bf16_(L["qut"]), L["qv"],
+             to_bf16_(L["qvt"]), L["k"], to_bf16_(L["kt"]), to_bf16_(L["v"]), L["Ph"], to_bf16_(L["Pt"]), L["o16"], do16, L["lse"],
+             Dtmp, dOh, dOt, dqkv, dSt, Pst, dP, sink["pos_bias_u"], sink["pos_bias_v"],
+             B, H, T, Tpad, Rpad, 1 if train else 0, is_f16(L["qu"]), o_kind(L["o16"]), *(() if hwt is None else (hwt,)))
+        del dSt, Pst, dOh, dOt, do16
+        if train:
+            dPT = E(Da, Rpad, dt=BF16)
+            transpose_bf16(dP, Rpad, Da, dPT)
+            gemm_dw(dPT, posT16, sink["linear_pos"])
+            self._dw_accum(dqkv, L["y16"], M, *sink["in_proj"], k_in=Dm)
+        if residual is not None:       # (+ the gradient through the residual from the normalised input)
+            gemm_nt(dqkv, W[pa + "in_proj.weight"].wt, EPI_F32_RESID, res=residual, outF=residual)
+            return residual
+        dy = E(M, Dm)
+        gemm_nt(dqkv, W[pa + "in_proj.weight"].wt, EPI_F32, outF=dy)
+        return dy
+
     def _decoder_bwd(self, W, dctx, g, G, trainable):
         m = self.m
-        B, T, Tpad, Rpad = dctx["B"], dctx["T"], dctx["Tpad"], dctx["Rpad"]
+        B, T = dctx["B"], dctx["T"]
         M = B * T
-        Mpad = pad64(M)
         dev = g.device
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        Z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
-        pos16, posT16, _ = self._pos(T, dev)
+        _, posT16, _ = self._pos(T, dev)
+        hwt = band_half_width(m, dev, T)
+        Gl = G if trainable else (lambda n: None)
         g = g.contiguous()
         for li in range(m.decoder_layer_num - 1, -1, -1):
             p = f"decoder.encoder_blocks.{li}."
+            pa = p + "attn."
             L = dctx["layers"][li]
-            Gl = G if trainable else (lambda n: None)
             g2 = g.view(M, D)
             # MLP branch
             dln = self._mlp_bwd(W, p + "mlp.fc1", p + "mlp.fc2", g2, L["h2"], L["hpre"], L["act"], M, Gl, residual=None)
@@ -1354,38 +1392,8 @@ class SedEngine:
                  Gl(p + "norm2.weight"), Gl(p + "norm2.bias"), M, D)
             del dln
             # attention branch: x1 = y + out_proj(relattn(y)),  y = LN1(in_scale * x_in)
-            g16 = self._dw_accum(g2, L["o16s"] if L.get("o16s") is not None else L["o16"], M,
-                                 G(p + "attn.out_proj.weight") if trainable else None, Gl(p + "attn.out_proj.bias"), k_in=D)
-            do16 = E(M, D, dt=BF16)
-            gemm_nt(g16, W[p + "attn.out_proj.weight"].wt, EPI_BF16, outH=do16)
-            dqkv = E(M, 3 * D, dt=BF16)
-            Dtmp = E(B * H, T)
-            dOh = E(B * H, T, 64, dt=BF16)
-            dOt = E(B * H, 64, Tpad, dt=BF16)
-            dSt = self._zeros(("dSt", B, Tpad), (B * H, Tpad, Tpad), BF16, dev)      # scratch of this call: one buffer for all layers
-            # P^T slab beside it: dK / dV as contractions over the two stored slabs (SED_RELPOS_DKDV=recompute: the score-recomputing kernel)
-            Pst = self._zeros(("Pst", B, Tpad), (B * H, Tpad, Tpad), BF16, dev) if self.relpos_stream else None
-            dP = Z(Rpad, D)
-            du = Gl(p + "attn.pos_bias_u")
-            dv = Gl(p + "attn.pos_bias_v")
-            scratch_uv = Z(2, D)
-            f16 = is_f16(L["qu"])
-            # (local window: the pooled slabs may hold the full-window content of an earlier call outside the band -- the band kernels
-            #  neither write nor read those tiles, see relpos_attention.hip band_tile_lo / band_tile_hi)
-            hwt = band_half_width(m, dev, T)
-            call("sed_relpos_attn_bwd" if hwt is None else "sed_relpos_attn_band_bwd", L["qu"], to_bf16_(L["qut"]), L["qv"],
-                 to_bf16_(L["qvt"]), L["k"], to_bf16_(L["kt"]), to_bf16_(L["v"]), L["Ph"], to_bf16_(L["Pt"]), L["o16"], do16, L["lse"],
-                 Dtmp, dOh, dOt, dqkv, dSt, Pst, dP, du if du is not None else scratch_uv[0], dv if dv is not None else scratch_uv[1],
-                 B, H, T, Tpad, Rpad, 1 if trainable else 0, f16, o_kind(L["o16"]), *(() if hwt is None else (hwt,)))
-            del dSt, Pst, dOh, dOt, do16
-            if trainable:
-                dPT = E(D, Rpad, dt=BF16)
-                transpose_bf16(dP, Rpad, D, dPT)
-                gemm_dw(dPT, posT16, G(p + "attn.linear_pos.weight"))
-                self._dw_accum(dqkv, L["y16"], M, G(p + "attn.in_proj.weight"), G(p + "attn.in_proj.bias"), k_in=D)
-            # dy = g (residual from the normalised input) + dqkv @ W_in
-            gemm_nt(dqkv, W[p + "attn.in_proj.weight"].wt, EPI_F32_RESID, res=g2, outF=g2)
-            gnew = E(B, T, D)
+            self._relattn_bwd(W, pa, L, dctx, posT16, hwt, g2, self._relattn_sink(Gl, pa, dev), D, residual=g2)
+            gnew = torch.empty(B, T, D, dtype=F32, device=dev)
             call("sed_layernorm_bwd", g2, L["x_in"], L["mean1"], L["rstd1"], self.P(p + "norm1.weight"), L["in_scale"],
                  gnew.view(M, D), 0, Gl(p + "norm1.weight"), Gl(p + "norm1.bias"), M, D)
             g = gnew
@@ -1419,12 +1427,12 @@ class SedEngine:
 
     def _conformer_bwd(self, W, dctx, g, G, trainable):
         m = self.m
-        B, T, Tpad, Rpad = dctx["B"], dctx["T"], dctx["Tpad"], dctx["Rpad"]
+        B, T = dctx["B"], dctx["T"]
         M = B * T
         dev = g.device
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        Z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
-        pos16, posT16, _ = self._pos(T, dev)
+        _, posT16, _ = self._pos(T, dev)
+        hwt = band_half_width(m, dev, T)
         Gl = G if trainable else (lambda n: None)
         g = g.contiguous()
         for li in range(m.decoder_layer_num - 1, -1, -1):
@@ -1450,36 +1458,10 @@ class SedEngine:
                  Gl(p + "norm_conv.weight"), Gl(p + "norm_conv.bias"), M, D)
             del dys, dxp
             # ---- attention
-            g16 = self._dw_accum(g2, L["o16s"] if L.get("o16s") is not None else L["o16"], M, Gl(pa + "out_proj.weight"),
-                                 Gl(pa + "out_proj.bias"), k_in=D)
-            do16 = E(M, D, dt=BF16)
-            gemm_nt(g16, W[pa + "out_proj.weight"].wt, EPI_BF16, outH=do16)
-            dqkv = E(M, 3 * D, dt=BF16)
-            Dtmp = E(B * H, T)
-            dOh = E(B * H, T, 64, dt=BF16)
-            dOt = E(B * H, 64, Tpad, dt=BF16)
-            dSt = self._zeros(("dSt", B, Tpad), (B * H, Tpad, Tpad), BF16, dev)
-            Pst = self._zeros(("Pst", B, Tpad), (B * H, Tpad, Tpad), BF16, dev) if self.relpos_stream else None
-            dP = Z(Rpad, D)
-            du, dv = Gl(pa + "pos_bias_u"), Gl(pa + "pos_bias_v")
-            scratch_uv = Z(2, D)
-            f16 = is_f16(L["qu"])
-            hwt = band_half_width(m, dev, T)
-            call("sed_relpos_attn_bwd" if hwt is None else "sed_relpos_attn_band_bwd", L["qu"], to_bf16_(L["qut"]), L["qv"],
-                 to_bf16_(L["qvt"]), L["k"], to_bf16_(L["kt"]), to_bf16_(L["v"]), L["Ph"], to_bf16_(L["Pt"]), L["o16"], do16, L["lse"],
-                 Dtmp, dOh, dOt, dqkv, dSt, Pst, dP, du if du is not None else scratch_uv[0], dv if dv is not None else scratch_uv[1],
-                 B, H, T, Tpad, Rpad, 1 if trainable else 0, f16, o_kind(L["o16"]), *(() if hwt is None else (hwt,)))
-            del dSt, Pst, dOh, dOt, do16
-            if trainable:
-                dPT = E(D, Rpad, dt=BF16)
-                transpose_bf16(dP, Rpad, D, dPT)
-                gemm_dw(dPT, posT16, G(pa + "linear_pos.weight"))
-                self._dw_accum(dqkv, L["y16"], M, G(pa + "in_proj.weight"), G(pa + "in_proj.bias"), k_in=D)
-            dln = E(M, D)
-            gemm_nt(dqkv, W[pa + "in_proj.weight"].wt, EPI_F32, outF=dln)
+            dln = self._relattn_bwd(W, pa, L, dctx, posT16, hwt, g2, self._relattn_sink(Gl, pa, dev), D, residual=None)
             call("sed_layernorm_bwd", dln, L["x1"], L["mean1"], L["rstd1"], self.P(p + "norm_mha.weight"), 1.0, g2, 1,
                  Gl(p + "norm_mha.weight"), Gl(p + "norm_mha.bias"), M, D)
-            del dln, dqkv
+            del dln
             self._swish_ffn_bwd(W, p + "feed_forward_macaron", p + "norm_ff_macaron", L["ffm"], g2, M, Gl)
             g = g2
             dctx["layers"][li] = None

@@ -20,8 +20,8 @@ import torch
 
 from . import ops
 
-from .engine import SedEngine, _W, D, H, version_key, band_half_width
-from .ops import BF16, F16, F32, call, h2d, gemm_nt, gemm_nt_cols, gemm_dw, gemm_dw_tn, dw_tn_ok, pad64, transpose_bf16, split3, is_f16, to_bf16_, o_kind
+from .engine import SedEngine, _W, D, H, version_key, band_half_width, in_split_precision
+from .ops import BF16, F16, F32, call, h2d, gemm_nt, gemm_nt_cols, gemm_dw, gemm_dw_tn, dw_tn_ok, pad64, transpose_bf16, split3, is_f16
 from .ops import EPI_F32, EPI_F32_RESID, EPI_BF16, EPI_GELU32
 
 HD_PAD = 64          # head width the attention kernels are built for
@@ -395,25 +395,16 @@ class PmamEngine(SedEngine):
         return feat, dict(layers=layers, Tc=Hc)
 
     # ------------------------------------------------------------------ 384-wide context network on the 64-wide attention kernels
+    @in_split_precision
     def _decoder_fwd(self, W, x, save):
         m = self.m
         dev = x.device
         B, T, Dd = x.shape
-        Dp = H * HD_PAD
-        Tpad = pad64(T)
         M = B * T
-        pos16, posT16, Rpad = self._pos(T, dev, Dd)
+        pos16, _, Rpad = self._pos(T, dev, Dd)
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        A16 = self.act
-        ctx = dict(B=B, T=T, Tpad=Tpad, Rpad=Rpad, layers=[])
+        ctx = dict(B=B, T=T, Tpad=pad64(T), Rpad=Rpad, layers=[])
         cur = x
-        if not getattr(self, "_in_split", False):   # every GEMM of this forward runs on split-precision operands (3x K issued)
-            self._in_split = True
-            try:
-                with ops.split_precision():
-                    return self._decoder_fwd(W, x, save)
-            finally:
-                self._in_split = False
         hwt = band_half_width(m, dev, T)
         for li in range(m.decoder_layer_num):
             p = f"decoder.encoder_blocks.{li}."
@@ -423,39 +414,12 @@ class PmamEngine(SedEngine):
             mean1, rstd1 = (E(M), E(M)) if save else (None, None)
             call("sed_ln_fwd_any", cur, self.P(p + "norm1.weight"), self.P(p + "norm1.bias"), 1e-5, in_scale, None, y32, mean1, rstd1,
                  M, Dd, 1)
-            yop = split3(y32, M, Dd)
-            Ph = E(H, Rpad, 64, dt=A16)
-            Pt = torch.zeros(H, 64, Rpad, dtype=A16, device=dev) if save else None
-            ptmp = E(Rpad, Dp, dt=A16)
-            gemm_nt(pos16, W[p + "attn.linear_pos.weight"].ws, EPI_BF16, outH=ptmp)
-            Ph.copy_(ptmp.view(Rpad, H, 64).permute(1, 0, 2))
-            if save:
-                Pt.copy_(ptmp.view(Rpad, H, 64).permute(1, 2, 0))
-            B16 = BF16 if save else A16
-            qu, k = [E(B * H, T, 64, dt=A16) for _ in range(2)]
-            v = E(B * H, T, 64, dt=B16)
-            qv = E(B * H, T, 64, dt=A16)
-            use_pool = getattr(self, "_lease_ok", False) or not save
-            vt = self._zeros(("dec_vt", li, B, Tpad), (B * H, 64, Tpad), A16, dev, use_pool)
-            qut = kt = qvt = None
-            if save:
-                qut, kt, qvt = [self._zeros(("dec", li, j, B, Tpad), (B * H, 64, Tpad), B16, dev, use_pool) for j in range(3)]
-            call("sed_gemm_qkv", yop, W[p + "attn.in_proj.weight"].ws, aux["bin"], M, 3 * Dd, H, T, Tpad, qu, k, v, qut, kt, vt, qv, qvt,
-                 aux["u"], aux["v"], 3 if save else 1)
-            o32 = E(M, Dp)
-            lse = E(B * H, T)
-            o32s = E(M, 3 * Dp, dt=F16)
-            if hwt is None:
-                call("sed_relpos_attn_fwd", qu, qv, k, vt, Ph, o32, o32s, lse, B, H, T, Tpad, Rpad, 1, 1)
-            else:       # local window (decoder_win_len)
-                call("sed_relpos_attn_band_fwd", qu, qv, k, vt, Ph, o32, o32s, lse, B, H, T, Tpad, Rpad, 1, 1, hwt)
-            x1 = E(B, T, Dd)
-            gemm_nt(o32s, W[p + "attn.out_proj.weight"].ws, EPI_F32_RESID, bias=self.P(p + "attn.out_proj.bias"), res=y32,
-                    outF=x1)
+            # (the weights at this prefix are the padded-head images: the shared attention path runs H * HD_PAD wide)
+            x1, att = self._relattn_fwd(W, p + "attn.", li, ctx, pos16, hwt, split3(y32, M, Dd), y32, (aux["bin"], aux["u"], aux["v"]), save)
             h2 = E(M, Dd)
             mean2, rstd2 = (E(M), E(M)) if save else (None, None)
             call("sed_ln_fwd_any", x1, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-5, 1.0, None, h2, mean2, rstd2, M, Dd, 1)
-            hpre = E(M, Dd, dt=B16)
+            hpre = E(M, Dd, dt=BF16 if save else self.act)      # (read by the backward only)
             act = E(M, Dd)
             h2 = split3(h2, M, Dd)
             gemm_nt(h2, W[p + "mlp.fc1.weight"].ws, EPI_GELU32, bias=self.P(p + "mlp.fc1.bias"), outH=hpre, outF=act)
@@ -465,9 +429,8 @@ class PmamEngine(SedEngine):
             if save:
                 # y16 / h2 / act / o16s are the [M, 3 K] split-precision images the forward GEMMs consumed; their first third is the f16
                 # operand of the weight gradients (TN kernel, engine.py `_dw_accum`) -- no fp32 copies saved, no transposes in the backward
-                ctx["layers"].append(dict(x_in=cur, in_scale=in_scale, y16=yop, mean1=mean1, rstd1=rstd1, Ph=Ph, Pt=Pt, qu=qu,
-                                          qut=qut, qv=qv, qvt=qvt, k=k, kt=kt, v=v, o16=o32, o16s=o32s, lse=lse, x1=x1, h2=h2, mean2=mean2,
-                                          rstd2=rstd2, hpre=hpre, act=act))
+                ctx["layers"].append(dict(att, x_in=cur, in_scale=in_scale, mean1=mean1, rstd1=rstd1, x1=x1, h2=h2, mean2=mean2, rstd2=rstd2,
+                                          hpre=hpre, act=act))
             cur = x2
         return cur, ctx
 
@@ -814,50 +777,33 @@ class PmamEngine(SedEngine):
 
     def _decoder_bwd(self, W, dctx, g, G, trainable, slots):
         m = self.m
-        B, T, Tpad, Rpad = dctx["B"], dctx["T"], dctx["Tpad"], dctx["Rpad"]
-        Dd, hd = m.decoder_dim, m.decoder_dim // H
+        B, T = dctx["B"], dctx["T"]
+        Dd = m.decoder_dim
         Dp = H * HD_PAD
         M = B * T
         dev = g.device
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        Z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
-        pos16, posT16, _ = self._pos(T, dev, Dd)
+        Z = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
+        _, posT16, _ = self._pos(T, dev, Dd)
+        hwt = band_half_width(m, dev, T)
+        Gl = G if trainable else (lambda n: None)
         g = g.contiguous()
         for li in range(m.decoder_layer_num - 1, -1, -1):
             p = f"decoder.encoder_blocks.{li}."
             L = dctx["layers"][li]
-            Gl = G if trainable else (lambda n: None)
             g2 = g.view(M, Dd)
             dln = self._mlp_bwd(W, p + "mlp.fc1", p + "mlp.fc2", g2, L["h2"], L["hpre"], L["act"], M, Gl, residual=None)
             call("sed_ln_bwd_any", dln, L["x1"], L["mean2"], L["rstd2"], self.P(p + "norm2.weight"), 1.0, g2, 1, Gl(p + "norm2.weight"),
                  Gl(p + "norm2.bias"), M, Dd)
             del dln
-            gwo = slots[("gwo", li)].view(Dd, Dp) if trainable else None
-            g16 = self._dw_accum(g2, L["o16s"], M, gwo, Gl(p + "attn.out_proj.bias"))
-            do16 = E(M, Dp, dt=BF16)
-            gemm_nt(g16, W[p + "attn.out_proj.weight"].wt, EPI_BF16, outH=do16)
-            dqkv = E(M, 3 * Dp, dt=BF16)
-            Dtmp = E(B * H, T)
-            dOh = E(B * H, T, 64, dt=BF16)
-            dOt = E(B * H, 64, Tpad, dt=BF16)
-            dSt = self._zeros(("dSt", B, Tpad), (B * H, Tpad, Tpad), BF16, dev)
-            Pst = self._zeros(("Pst", B, Tpad), (B * H, Tpad, Tpad), BF16, dev) if self.relpos_stream else None
-            dP = Z(Rpad, Dp)
-            du, dv = (slots[("du", li)], slots[("dv", li)]) if trainable else (Z(Dp), Z(Dp))
-            hwt = band_half_width(m, dev, T)
-            call("sed_relpos_attn_bwd" if hwt is None else "sed_relpos_attn_band_bwd", L["qu"], to_bf16_(L["qut"]), L["qv"],
-                 to_bf16_(L["qvt"]), L["k"], to_bf16_(L["kt"]), to_bf16_(L["v"]), L["Ph"], to_bf16_(L["Pt"]), L["o16"], do16, L["lse"],
-                 Dtmp, dOh, dOt, dqkv, dSt, Pst, dP, du, dv, B, H, T, Tpad, Rpad, 1 if trainable else 0, 1, o_kind(L["o16"]),
-                 *(() if hwt is None else (hwt,)))
-            del dSt, Pst, dOh, dOt, do16
+            # gradient images (padded heads) in the zeroed slots of `_grad_slots`; one scatter launch after the loop un-pads them
             if trainable:
-                # gradient images (padded heads) in the zeroed slots of `_grad_slots`; one scatter launch after the loop un-pads them
-                dPT = E(Dp, Rpad, dt=BF16)
-                transpose_bf16(dP, Rpad, Dp, dPT)
-                gemm_dw(dPT, posT16, slots[("gwp", li)].view(Dp, Dd))
-                self._dw_accum(dqkv, L["y16"], M, slots[("gwi", li)].view(3 * Dp, Dd), slots[("gbi", li)])
-            gemm_nt(dqkv, W[p + "attn.in_proj.weight"].wt, EPI_F32_RESID, res=g2, outF=g2)
-            gnew = E(B, T, Dd)
+                sink = dict(out_proj=(slots[("gwo", li)].view(Dd, Dp), G(p + "attn.out_proj.bias")), linear_pos=slots[("gwp", li)].view(Dp, Dd),
+                            in_proj=(slots[("gwi", li)].view(3 * Dp, Dd), slots[("gbi", li)]),
+                            pos_bias_u=slots[("du", li)], pos_bias_v=slots[("dv", li)])
+            else:
+                sink = dict(out_proj=(None, None), linear_pos=None, in_proj=(None, None), pos_bias_u=Z(Dp), pos_bias_v=Z(Dp))
+            self._relattn_bwd(W, p + "attn.", L, dctx, posT16, hwt, g2, sink, None, residual=g2)
+            gnew = torch.empty(B, T, Dd, dtype=F32, device=dev)
             call("sed_ln_bwd_any", g2, L["x_in"], L["mean1"], L["rstd1"], self.P(p + "norm1.weight"), L["in_scale"], gnew.view(M, Dd), 0,
                  Gl(p + "norm1.weight"), Gl(p + "norm1.bias"), M, Dd)
             g = gnew
