@@ -297,6 +297,20 @@ int sed_fpool_fwd(const float* x, const float* gamma, const float* beta, float e
                   float* rstd, int B, int tp, hipStream_t stream);
 int sed_fpool_bwd(const float* dpooled, const float* x, const float* mean, const float* rstd, const float* gamma,
                   float* dtok_tmp, float* dx_acc, float* dgamma, float* dbeta, int B, int tp, hipStream_t stream);
+/* the five entry points above for a sequence that holds F (1..12) of the 12 frequency rows of the patch grid -- structured frequency
+ * patchout, passt.py:533-547: N = 2 + F tp, cols / conv are [B F tp, .].  `rows`: DEVICE array of the F kept rows, strictly increasing
+ * values in [0, 12) (validated by the caller), or NULL for 0..F-1; it selects the mel rows, the frequency embedding added to kept row
+ * f' and the column of dfreq its gradient goes to (the other columns are not touched).  The entry points above are these with
+ * rows = NULL, F = 12.  F outside 1..12 returns SED_ERR_ARG. */
+int sed_im2col_rows(const float* mel, void* cols, const int* rows, int F, int B, int T, int tstart, int tp, int f16, hipStream_t stream);
+int sed_assemble_tokens_rows(const float* conv, const float* cls, const float* dist, const float* new_pos, const float* freq_pe,
+                             const float* time_pe, const int* rows, int F, int toffset, float* x, int B, int tp, hipStream_t stream);
+int sed_assemble_tokens_rows_bwd(const float* dx, void* dconv, float* dcls, float* ddist, float* dnew_pos, float* dfreq, float* dtime,
+                                 const int* rows, int F, int toffset, int B, int tp, hipStream_t stream);
+int sed_fpool_rows_fwd(const float* x, const float* gamma, const float* beta, float eps, float* pooled, float* mean, float* rstd,
+                       int B, int tp, int F, hipStream_t stream);
+int sed_fpool_rows_bwd(const float* dpooled, const float* x, const float* mean, const float* rstd, const float* gamma, float* dtok_tmp,
+                       float* dx_acc, float* dgamma, float* dbeta, int B, int tp, int F, hipStream_t stream);
 /* InterpolateModule linear x ratio (+ replicated last frame) (passt_sed.py:13-34,258-259) */
 int sed_interp_fwd(const float* in, float* out, int B, int tin, int pad, int ratio, hipStream_t stream);
 int sed_interp_bwd(const float* dout, float* din, int B, int tin, int pad, int ratio, hipStream_t stream);

@@ -256,37 +256,45 @@ extern "C" int sed_layernorm_bwd_x16(const float* dy, const float* x, const floa
 // ---------------------------------------------------------------------------------------------------
 // Patch embedding plumbing (passt.py:302-315, 503-569): im2col for the 16x16/stride-10 conv, token assembly.
 // ---------------------------------------------------------------------------------------------------
-// mel [B, 128, T] fp32 -> cols bf16 [B * 12 * tp, 256];  row (b, f, t), col 16 i + j = mel[b, 10 f + i, tstart + 10 t + j]
-// (tstart selects a sliding-window slab without copying it)
-__global__ void im2col_kernel(const float* __restrict__ mel, bf16_t* __restrict__ cols, int B, int T, int tstart,
-                              int tp, int f16) {
-    const size_t total = (size_t)B * 12 * tp * 128;  // pairs
+// mel [B, 128, T] fp32 -> cols bf16 [B * F * tp, 256];  row (b, f', t), col 16 i + j = mel[b, 10 rows[f'] + i, tstart + 10 t + j]
+// (tstart selects a sliding-window slab without copying it; `rows`: the F kept frequency rows of structured patchout, strictly
+//  increasing values in [0, 12), null = identity -- the gather sits here so that the patch-embedding GEMMs shrink with the sequence)
+__global__ void im2col_kernel(const float* __restrict__ mel, bf16_t* __restrict__ cols, const int* __restrict__ rows, int F, int B,
+                              int T, int tstart, int tp, int f16) {
+    const size_t total = (size_t)B * F * tp * 128;  // pairs
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int pr = (int)(idx & 127);
         const size_t row = idx >> 7;
-        const int t = (int)(row % tp), f = (int)((row / tp) % 12), b = (int)(row / ((size_t)tp * 12));
+        const int t = (int)(row % tp), fk = (int)((row / tp) % F), b = (int)(row / ((size_t)tp * F));
+        const int f = rows != nullptr ? rows[fk] : fk;
         const int i = pr >> 3, j = (pr & 7) * 2;
         const float* src = mel + ((size_t)b * 128 + 10 * f + i) * T + tstart + 10 * t + j;
         reinterpret_cast<unsigned*>(cols)[idx] = f16 ? pack2<true>(src[0], src[1]) : pack2bf(src[0], src[1]);
     }
 }
-extern "C" int sed_im2col(const float* mel, void* cols, int B, int T, int tstart, int tp, int f16, hipStream_t stream) {
+extern "C" int sed_im2col_rows(const float* mel, void* cols, const int* rows, int F, int B, int T, int tstart, int tp, int f16,
+                               hipStream_t stream) {
     (void)hipGetLastError();
-    if (tp < 1 || tstart < 0 || tstart + 10 * (tp - 1) + 16 > T) return SED_ERR_ARG;
-    hipLaunchKernelGGL(im2col_kernel, dim3(2048), dim3(256), 0, stream, mel, (bf16_t*)cols, B, T, tstart, tp, f16);
+    if (F < 1 || F > 12 || B < 1 || tp < 1 || tstart < 0 || tstart + 10 * (tp - 1) + 16 > T) return SED_ERR_ARG;
+    hipLaunchKernelGGL(im2col_kernel, dim3(2048), dim3(256), 0, stream, mel, (bf16_t*)cols, rows, F, B, T, tstart, tp, f16);
     return sed_check_launch();
+}
+extern "C" int sed_im2col(const float* mel, void* cols, int B, int T, int tstart, int tp, int f16, hipStream_t stream) {
+    return sed_im2col_rows(mel, cols, nullptr, 12, B, T, tstart, tp, f16, stream);
 }
 // d mel is never needed (the mel input is data).
 
-// conv [B * 12 * tp, D] (bias already added) -> x [B, 2 + 12 tp, D] with the three positional tables.
+// conv [B * F * tp, D] (bias already added) -> x [B, 2 + F tp, D] with the three positional tables; kept row f' carries the
+// frequency embedding of grid row rows[f'] (the reference adds the tables first and drops rows afterwards, passt.py:517-539).
 // freq_pe [D, 12], time_pe [D, 99] in the reference's checkpoint layout ([1,D,12,1] / [1,D,1,99]).
 // One workgroup per token position n: the position's additive row (cls / dist + new_pos, or time_pe + freq_pe -- a strided gather
 // from the checkpoint layout) is fetched once into registers and reused for all B clips; rows move as float4.
 __global__ __launch_bounds__(256) void assemble_tokens_kernel(const float* __restrict__ conv, const float* __restrict__ cls,
                                                               const float* __restrict__ dist, const float* __restrict__ new_pos,
                                                               const float* __restrict__ freq_pe, const float* __restrict__ time_pe,
-                                                              int toffset, float* __restrict__ x, int B, int tp) {
-    const int N = 2 + 12 * tp, n = blockIdx.x;
+                                                              const int* __restrict__ rows, int F, int toffset,
+                                                              float* __restrict__ x, int B, int tp) {
+    const int N = 2 + F * tp, n = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     Row pe;
     if (n < 2) {
@@ -298,7 +306,8 @@ __global__ __launch_bounds__(256) void assemble_tokens_kernel(const float* __res
         for (int bi = wave; bi < B; bi += 4) row_store(pe, x + ((size_t)bi * N + n) * DM, lane);
         return;
     }
-    const int p = n - 2, f = p / tp, t = p - f * tp;
+    const int p = n - 2, fk = p / tp, t = p - fk * tp;
+    const int f = rows != nullptr ? rows[fk] : fk;
 #pragma unroll
     ROW_FOREACH(i, k) {
         const int d = 4 * (lane + 64 * i) + k;
@@ -306,33 +315,40 @@ __global__ __launch_bounds__(256) void assemble_tokens_kernel(const float* __res
     }
     for (int bi = wave; bi < B; bi += 4) {
         Row r;
-        row_load(r, conv + ((size_t)bi * 12 * tp + p) * DM, lane);
+        row_load(r, conv + ((size_t)bi * F * tp + p) * DM, lane);
 #pragma unroll
         ROW_FOREACH(i, k) f4(r.v[i], k) += f4(pe.v[i], k);
         row_store(r, x + ((size_t)bi * N + n) * DM, lane);
     }
 }
+extern "C" int sed_assemble_tokens_rows(const float* conv, const float* cls, const float* dist, const float* new_pos,
+                                        const float* freq_pe, const float* time_pe, const int* rows, int F, int toffset, float* x,
+                                        int B, int tp, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (F < 1 || F > 12 || B < 1 || tp < 1 || toffset < 0 || toffset + tp > 99) return SED_ERR_ARG;
+    hipLaunchKernelGGL(assemble_tokens_kernel, dim3(2 + F * tp), dim3(256), 0, stream, conv, cls, dist, new_pos, freq_pe,
+                       time_pe, rows, F, toffset, x, B, tp);
+    return sed_check_launch();
+}
 extern "C" int sed_assemble_tokens(const float* conv, const float* cls, const float* dist, const float* new_pos,
                                    const float* freq_pe, const float* time_pe, int toffset, float* x, int B, int tp,
                                    hipStream_t stream) {
-    (void)hipGetLastError();
-    if (tp < 1 || toffset < 0 || toffset + tp > 99) return SED_ERR_ARG;
-    hipLaunchKernelGGL(assemble_tokens_kernel, dim3(2 + 12 * tp), dim3(256), 0, stream, conv, cls, dist, new_pos, freq_pe,
-                       time_pe, toffset, x, B, tp);
-    return sed_check_launch();
+    return sed_assemble_tokens_rows(conv, cls, dist, new_pos, freq_pe, time_pe, nullptr, 12, toffset, x, B, tp, stream);
 }
-// backward: dx [B, N, D] -> dconv bf16 rows (GEMM operand), d cls/dist/new_pos, d freq_pe, d time_pe (atomics)
+// backward: dx [B, N, D] -> dconv bf16 rows (GEMM operand), d cls/dist/new_pos, d freq_pe, d time_pe (atomics); the columns of
+// d freq_pe that belong to dropped rows are never touched
 __global__ void assemble_tokens_bwd_kernel(const float* __restrict__ dx, bf16_t* __restrict__ dconv,
                                            float* __restrict__ dcls, float* __restrict__ ddist,
                                            float* __restrict__ dnew_pos, float* __restrict__ dfreq,
-                                           float* __restrict__ dtime, int toffset, int B, int tp) {
+                                           float* __restrict__ dtime, const int* __restrict__ rows, int F, int toffset, int B,
+                                           int tp) {
     // one block per (f or token-pair or time column, d-chunk, batch slice): partial sums over the slice's clips in registers,
     // then one atomic per output (the batch slices run in parallel: a single block per job walked B * tp rows back to back)
-    const int N = 2 + 12 * tp;
+    const int N = 2 + F * tp;
     const int d = blockIdx.y * 256 + threadIdx.x;
     if (d >= DM) return;
     const int bper = (B + gridDim.z - 1) / gridDim.z, b0 = blockIdx.z * bper, b1 = (b0 + bper < B) ? b0 + bper : B;
-    const int job = blockIdx.x;  // 0: cls/dist, 1..12: freq row f = job-1 (also writes dconv), 13..: time cols
+    const int job = blockIdx.x;  // 0: cls/dist, 1..F: kept freq row f' = job-1 (also writes dconv), F+1..: time cols
     if (job == 0) {
         float a = 0.f, c = 0.f;
         for (int b = b0; b < b1; ++b) {
@@ -343,50 +359,58 @@ __global__ void assemble_tokens_bwd_kernel(const float* __restrict__ dx, bf16_t*
         if (dcls != nullptr) unsafeAtomicAdd(&dcls[d], a);
         if (ddist != nullptr) unsafeAtomicAdd(&ddist[d], c);
         if (dnew_pos != nullptr) { unsafeAtomicAdd(&dnew_pos[d], a); unsafeAtomicAdd(&dnew_pos[DM + d], c); }
-    } else if (job <= 12) {
-        const int f = job - 1;
+    } else if (job <= F) {
+        const int fk = job - 1;
         float a = 0.f;
         for (int b = b0; b < b1; ++b)
             for (int t = 0; t < tp; ++t) {
-                const float v = dx[((size_t)b * N + 2 + f * tp + t) * DM + d];
+                const float v = dx[((size_t)b * N + 2 + fk * tp + t) * DM + d];
                 a += v;
-                dconv[((size_t)b * 12 * tp + f * tp + t) * DM + d] = f2bf(v);
+                dconv[((size_t)b * F * tp + fk * tp + t) * DM + d] = f2bf(v);
             }
-        if (dfreq != nullptr) unsafeAtomicAdd(&dfreq[d * 12 + f], a);
+        if (dfreq != nullptr) unsafeAtomicAdd(&dfreq[d * 12 + (rows != nullptr ? rows[fk] : fk)], a);
     } else {
-        const int t = job - 13;
+        const int t = job - 1 - F;
         if (dtime == nullptr) return;
         float a = 0.f;
         for (int b = b0; b < b1; ++b)
-            for (int f = 0; f < 12; ++f) a += dx[((size_t)b * N + 2 + f * tp + t) * DM + d];
+            for (int fk = 0; fk < F; ++fk) a += dx[((size_t)b * N + 2 + fk * tp + t) * DM + d];
         unsafeAtomicAdd(&dtime[d * 99 + toffset + t], a);
     }
 }
+extern "C" int sed_assemble_tokens_rows_bwd(const float* dx, void* dconv, float* dcls, float* ddist, float* dnew_pos, float* dfreq,
+                                            float* dtime, const int* rows, int F, int toffset, int B, int tp,
+                                            hipStream_t stream) {
+    (void)hipGetLastError();
+    if (F < 1 || F > 12 || B < 1 || tp < 1 || toffset < 0 || toffset + tp > 99) return SED_ERR_ARG;
+    hipLaunchKernelGGL(assemble_tokens_bwd_kernel, dim3(1 + F + tp, DM / 256, B < 8 ? B : 8), dim3(256), 0, stream, dx,
+                       (bf16_t*)dconv, dcls, ddist, dnew_pos, dfreq, dtime, rows, F, toffset, B, tp);
+    return sed_check_launch();
+}
 extern "C" int sed_assemble_tokens_bwd(const float* dx, void* dconv, float* dcls, float* ddist, float* dnew_pos,
                                        float* dfreq, float* dtime, int toffset, int B, int tp, hipStream_t stream) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(assemble_tokens_bwd_kernel, dim3(13 + tp, DM / 256, B < 8 ? B : 8), dim3(256), 0, stream, dx, (bf16_t*)dconv,
-                       dcls, ddist, dnew_pos, dfreq, dtime, toffset, B, tp);
-    return sed_check_launch();
+    return sed_assemble_tokens_rows_bwd(dx, dconv, dcls, ddist, dnew_pos, dfreq, dtime, nullptr, 12, toffset, B, tp, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------
-// f_pool (passt_sed.py:199-218, 'mean_pool'):  pooled[b, t] = mean_f LN_out_norm(x[b, 2 + f tp + t])
+// f_pool (passt_sed.py:199-218, 'mean_pool'):  pooled[b, t] = mean_f' LN_out_norm(x[b, 2 + f' tp + t]) over the F rows the
+// sequence holds (12, or the kept rows of structured patchout; which rows they are does not matter here).  `inv_f` = 1 / F, rounded
+// on the host.
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fpool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float eps,
                                                         float* __restrict__ pooled, float* __restrict__ mean,
-                                                        float* __restrict__ rstd, int B, int tp) {
+                                                        float* __restrict__ rstd, int B, int tp, int F, float inv_f) {
     const int lane = threadIdx.x & 63;
     const int job = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (job >= B * tp) return;
-    const int b = job / tp, t = job - b * tp, N = 2 + 12 * tp;
+    const int b = job / tp, t = job - b * tp, N = 2 + F * tp;
     Row g, bt, acc;
     row_load(g, gamma, lane);
     row_load(bt, beta, lane);
 #pragma unroll
     ROW_FOREACH(i, c) f4(acc.v[i], c) = 0.f;
-    for (int f = 0; f < 12; ++f) {
+    for (int f = 0; f < F; ++f) {
         const size_t tok = (size_t)b * N + 2 + f * tp + t;
         Row r;
         row_load_nt(r, x + tok * DM, lane);
@@ -403,21 +427,26 @@ __global__ __launch_bounds__(256) void fpool_fwd_kernel(const float* __restrict_
         if (lane == 0 && mean != nullptr) { mean[tok] = mu; rstd[tok] = rs; }
     }
 #pragma unroll
-    ROW_FOREACH(i, c) f4(acc.v[i], c) *= (1.0f / 12.0f);
+    ROW_FOREACH(i, c) f4(acc.v[i], c) *= inv_f;
     row_store(acc, pooled + (size_t)job * DM, lane);
+}
+extern "C" int sed_fpool_rows_fwd(const float* x, const float* gamma, const float* beta, float eps, float* pooled, float* mean,
+                                  float* rstd, int B, int tp, int F, hipStream_t stream) {
+    (void)hipGetLastError();
+    if (F < 1 || F > 12 || B < 1 || tp < 1) return SED_ERR_ARG;
+    hipLaunchKernelGGL(fpool_fwd_kernel, dim3(cdiv(B * tp, 4)), dim3(256), 0, stream, x, gamma, beta, eps, pooled, mean,
+                       rstd, B, tp, F, 1.0f / (float)F);
+    return sed_check_launch();
 }
 extern "C" int sed_fpool_fwd(const float* x, const float* gamma, const float* beta, float eps, float* pooled,
                              float* mean, float* rstd, int B, int tp, hipStream_t stream) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(fpool_fwd_kernel, dim3(cdiv(B * tp, 4)), dim3(256), 0, stream, x, gamma, beta, eps, pooled, mean,
-                       rstd, B, tp);
-    return sed_check_launch();
+    return sed_fpool_rows_fwd(x, gamma, beta, eps, pooled, mean, rstd, B, tp, 12, stream);
 }
-// backward = LayerNorm backward of the 12 B tp token rows with dy = dpooled[b, t] / 12, dx accumulated into the
-// residual-stream gradient at rows 2 + f tp + t.  Implemented by expanding dpooled to token rows (cheap) and
-// calling the LN backward kernel with dy_scale = 1/12.
-__global__ void fpool_expand_kernel(const float* __restrict__ dpooled, float* __restrict__ dtok, int B, int tp) {
-    const int N = 2 + 12 * tp;
+// backward = LayerNorm backward of the F B tp token rows with dy = dpooled[b, t] / F, dx accumulated into the
+// residual-stream gradient at rows 2 + f' tp + t.  Implemented by expanding dpooled to token rows (cheap) and
+// calling the LN backward kernel with dy_scale = 1/F.
+__global__ void fpool_expand_kernel(const float* __restrict__ dpooled, float* __restrict__ dtok, int B, int tp, int F) {
+    const int N = 2 + F * tp;
     const size_t total = (size_t)B * N * (DM / 4);
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int d4 = (int)(idx % (DM / 4));
@@ -431,19 +460,25 @@ __global__ void fpool_expand_kernel(const float* __restrict__ dpooled, float* __
         reinterpret_cast<float4*>(dtok)[idx] = v;
     }
 }
-extern "C" int sed_fpool_bwd(const float* dpooled, const float* x, const float* mean, const float* rstd,
-                             const float* gamma, float* dtok_tmp, float* dx_acc, float* dgamma, float* dbeta, int B,
-                             int tp, hipStream_t stream) {
+extern "C" int sed_fpool_rows_bwd(const float* dpooled, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                  float* dtok_tmp, float* dx_acc, float* dgamma, float* dbeta, int B, int tp, int F,
+                                  hipStream_t stream) {
     (void)hipGetLastError();
-    const int N = 2 + 12 * tp, M = B * N;
-    hipLaunchKernelGGL(fpool_expand_kernel, dim3(2048), dim3(256), 0, stream, dpooled, dtok_tmp, B, tp);
+    if (F < 1 || F > 12 || B < 1 || tp < 1) return SED_ERR_ARG;
+    const int N = 2 + F * tp, M = B * N;
+    hipLaunchKernelGGL(fpool_expand_kernel, dim3(2048), dim3(256), 0, stream, dpooled, dtok_tmp, B, tp, F);
     // rows 0,1 of every clip have dy = 0 (and mean/rstd never written there -> use finite placeholders: the host
     // zero-fills mean/rstd once); their contribution is exactly 0 * finite.
     int blocks = cdiv(M, 4);
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(blocks), dim3(256), 0, stream, (const float*)dtok_tmp, x, mean, rstd,
-                       gamma, 1.0f, dx_acc, 1, dgamma, dbeta, M, 1.0f / 12.0f);
+                       gamma, 1.0f, dx_acc, 1, dgamma, dbeta, M, 1.0f / (float)F, (bf16_t*)nullptr);
     return sed_check_launch();
+}
+extern "C" int sed_fpool_bwd(const float* dpooled, const float* x, const float* mean, const float* rstd,
+                             const float* gamma, float* dtok_tmp, float* dx_acc, float* dgamma, float* dbeta, int B,
+                             int tp, hipStream_t stream) {
+    return sed_fpool_rows_bwd(dpooled, x, mean, rstd, gamma, dtok_tmp, dx_acc, dgamma, dbeta, B, tp, 12, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------

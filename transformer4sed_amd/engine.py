@@ -351,33 +351,37 @@ class SedEngine:
         return (ent[3] if (self.split and not (self.dec_terms2 and want_plain)) else ent[0]), ent[1], ent[2]
 
     # ------------------------------------------------------------------ encoder
-    def _encoder_fwd(self, W, mel, tstarts, tp, toffsets, save, want_frame):
+    def _encoder_fwd(self, W, mel, tstarts, tp, toffsets, save, want_frame, rows=None, F=12):
         """PaSST encoder on `len(tstarts)` slabs of every clip (slabs folded into the batch, slab-major).
-        mel [B,128,T]; returns pooled [nS*B, tp, D] (f_pool of layer `feature_layer`), frame16 (final norm), ctx."""
+        mel [B,128,T]; returns pooled [nS*B, tp, D] (f_pool of layer `feature_layer`), frame16 (final norm), ctx.
+        `rows`: per slab the device int32 [F] kept frequency rows of structured patchout (None: all 12); the sequence is then
+        N = 2 + F tp tokens from the im2col on -- every kernel below takes N."""
         m = self.m
         dev = mel.device
         B, _, T = mel.shape
         nS = len(tstarts)
         Bx = nS * B
-        N = 2 + 12 * tp
+        N = 2 + F * tp
         Npad = pad64(N)
         M = Bx * N
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         A16 = self.act
         f16 = 1 if A16 == F16 else 0
-        ctx = dict(B=Bx, N=N, Npad=Npad, tp=tp, layers=[], toffsets=toffsets, nS=nS)
-        cols = E(Bx * 12 * tp, 256, dt=A16)
+        rows = [None] * nS if rows is None else rows
+        ctx = dict(B=Bx, N=N, Npad=Npad, tp=tp, layers=[], toffsets=toffsets, nS=nS, F=F, rows=rows)
+        Ms = B * F * tp             # patch rows of one slab
+        cols = E(nS * Ms, 256, dt=A16)
         for s, ts in enumerate(tstarts):
-            call("sed_im2col", mel, cols[s * B * 12 * tp:(s + 1) * B * 12 * tp], B, T, ts, tp, f16)
-        conv = E(Bx * 12 * tp, D)
+            call("sed_im2col_rows", mel, cols[s * Ms:(s + 1) * Ms], rows[s], F, B, T, ts, tp, f16)
+        conv = E(nS * Ms, D)
         gemm_nt(cols, W["backbone.patch_embed.proj.weight"].w, EPI_F32, bias=self.P("backbone.patch_embed.proj.bias"),
                 outF=conv)
         x = E(Bx, N, D)
         fpe = self.P("backbone.freq_new_pos_embed").reshape(D, 12)
         tpe = self.P("backbone.time_new_pos_embed").reshape(D, 99)
         for s in range(nS):
-            call("sed_assemble_tokens", conv[s * B * 12 * tp:(s + 1) * B * 12 * tp], self.P("backbone.cls_token"),
-                 self.P("backbone.dist_token"), self.P("backbone.new_pos_embed"), fpe, tpe, int(toffsets[s]),
+            call("sed_assemble_tokens_rows", conv[s * Ms:(s + 1) * Ms], self.P("backbone.cls_token"),
+                 self.P("backbone.dist_token"), self.P("backbone.new_pos_embed"), fpe, tpe, rows[s], F, int(toffsets[s]),
                  x[s * B:(s + 1) * B], B, tp)
         if save:
             ctx["cols"] = cols
@@ -618,13 +622,15 @@ class SedEngine:
         return pooled, frame16, ctx
 
     def _fpool_fwd(self, W, x, Bx, tp, save, ctx):
-        """'mean_pool' frequency pooling (passt_sed.py:199-210): out_norm + mean over the 12 frequency rows -> [Bx, tp, D]."""
+        """'mean_pool' frequency pooling (passt_sed.py:199-210): out_norm + mean over the frequency rows of the sequence (12, or the
+        kept ones of structured patchout) -> [Bx, tp, D]."""
         dev = x.device
-        M = Bx * (2 + 12 * tp)
+        F = ctx["F"]
+        M = Bx * (2 + F * tp)
         pooled = torch.empty(Bx, tp, D, dtype=F32, device=dev)
         pm = torch.zeros(M, device=dev) if save else None
         pr = torch.zeros(M, device=dev) if save else None
-        call("sed_fpool_fwd", x, self.P("out_norm.weight"), self.P("out_norm.bias"), 1e-5, pooled, pm, pr, Bx, tp)
+        call("sed_fpool_rows_fwd", x, self.P("out_norm.weight"), self.P("out_norm.bias"), 1e-5, pooled, pm, pr, Bx, tp, F)
         if save:
             ctx.update(pool_x=x, pool_mean=pm, pool_rstd=pr)
         return pooled
@@ -832,7 +838,9 @@ class SedEngine:
 
     # ------------------------------------------------------------------ full forward
     def forward(self, mel, encoder_win=False, mix_rate=0.5, win_param=(512, 49), temp_w=1.0, pad_mask=None,
-                mlm_plan=None, toffsets=None, save=False):
+                mlm_plan=None, toffsets=None, rows=None, save=False):
+        """`rows`: structured frequency patchout (passt.py:533-547) -- the kept frequency rows of every backbone call of this forward
+        as lists of ints, the global pass first, then one set per sliding window in sweep order; None: nothing is dropped."""
         m = self.m
         dev = mel.device
         if mel.dtype != F32 or not mel.is_contiguous():
@@ -844,7 +852,17 @@ class SedEngine:
         out = {}
         tp = (T - 16) // 10 + 1
         tp = min(tp, 99)
-        pooled, frame16, ectx = self._encoder_fwd(W, mel, [0], tp, [0], save, want_frame=m.has_at)
+        F, rows_dev = 12, None
+        if rows is not None:
+            F = len(rows[0])
+            n_sets = 1 + (len(window_starts(T, win_param[0], win_param[1])) if encoder_win else 0)
+            # (checked on the host: the kernels index the mel rows and the frequency table with these values)
+            if len(rows) != n_sets or not 1 <= F <= 12 or any(
+                    len(r) != F or min(r) < 0 or max(r) >= 12 or any(a >= b for a, b in zip(r, r[1:])) for r in rows):
+                raise ValueError(f"rows: expected {n_sets} sets of equally many strictly increasing frequency rows in [0, 12), got {rows!r}")
+            rows_dev = h2d(rows, torch.int32, dev)      # [1 + windows, F]: one upload for every row set of this forward
+        pooled, frame16, ectx = self._encoder_fwd(W, mel, [0], tp, [0], save, want_frame=m.has_at,
+                                                  rows=None if rows is None else [rows_dev[0]], F=F)
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         ratio = m.decode_ratio
         pad = 1  # 99 -> 100 frames (passt_sed.py:258)
@@ -868,7 +886,7 @@ class SedEngine:
             wgroups = []
             for tpw, wis in groups.items():
                 pw, _, gctx = self._encoder_fwd(W, mel, [starts[w] for w in wis], tpw, [toffsets[w] for w in wis], save,
-                                                want_frame=False)
+                                                want_frame=False, rows=None if rows is None else [rows_dev[1 + w] for w in wis], F=F)
                 chunks.append(pw.view(-1, D))
                 wgroups.append(dict(ectx=gctx, row0=row, rows=len(wis) * B * tpw))
                 for k, w in enumerate(wis):
@@ -1141,7 +1159,7 @@ class SedEngine:
         layer, the blocks from the top saved one down to the lowest trainable one, then the patch embedding.  `genc` is the gradient
         arriving at the top of the stack (AT head) or None; gradients accumulate into the arena views."""
         m = self.m
-        B, N, tp = ectx["B"], ectx["N"], ectx["tp"]
+        B, N, tp, F = ectx["B"], ectx["N"], ectx["tp"], ectx["F"]
         dev = dpooled.device
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         Z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
@@ -1152,8 +1170,8 @@ class SedEngine:
         gpool = Z(B, N, D) if need_pool_dx else None
         dtok_tmp = E(B, N, D)
         pool_dx = gpool if need_pool_dx else Z(B, N, D)
-        call("sed_fpool_bwd", dpooled.contiguous(), ectx["pool_x"], ectx["pool_mean"], ectx["pool_rstd"], self.P("out_norm.weight"),
-             dtok_tmp, pool_dx, G("out_norm.weight"), G("out_norm.bias"), B, tp)
+        call("sed_fpool_rows_bwd", dpooled.contiguous(), ectx["pool_x"], ectx["pool_mean"], ectx["pool_rstd"], self.P("out_norm.weight"),
+             dtok_tmp, pool_dx, G("out_norm.weight"), G("out_norm.bias"), B, tp, F)
         if hook is not None:
             hook("heads")  # AT head, out_norm (and backbone.norm) gradients are final
         if lo >= depth:
@@ -1171,12 +1189,13 @@ class SedEngine:
         # patch embedding + positional tables (one slab of the batch per window / time offset)
         nS = ectx["nS"]
         Bs = B // nS
-        Mp = B * 12 * tp
+        Ms = Bs * F * tp
+        Mp = nS * Ms
         dconv16 = E(Mp, D, dt=BF16)
         for sidx in range(nS):
-            call("sed_assemble_tokens_bwd", genc[sidx * Bs:(sidx + 1) * Bs], dconv16[sidx * Bs * 12 * tp:(sidx + 1) * Bs * 12 * tp],
+            call("sed_assemble_tokens_rows_bwd", genc[sidx * Bs:(sidx + 1) * Bs], dconv16[sidx * Ms:(sidx + 1) * Ms],
                  G("backbone.cls_token"), G("backbone.dist_token"), G("backbone.new_pos_embed"), G("backbone.freq_new_pos_embed"),
-                 G("backbone.time_new_pos_embed"), int(ectx["toffsets"][sidx]), Bs, tp)
+                 G("backbone.time_new_pos_embed"), ectx["rows"][sidx], F, int(ectx["toffsets"][sidx]), Bs, tp)
         self._dw_accum(dconv16, ectx["cols"], Mp, G("backbone.patch_embed.proj.weight"), G("backbone.patch_embed.proj.bias"))
         if hook is not None:
             hook("embed")

@@ -93,11 +93,35 @@ class _PatchEmbed(_Holder):
         self.proj = nn.Conv2d(1, dim, kernel_size=16, stride=10)
 
 
+def patchout_f(s):
+    """`s_patchout_f` (passt.py:533-547: how many of the 12 frequency rows of the patch grid a training-mode backbone call drops) as a
+    checked int.  12 would leave an empty sequence (NaN in the reference) and is refused."""
+    if isinstance(s, bool) or not isinstance(s, int):
+        raise TypeError(f"s_patchout_f must be an int, got {s!r}")
+    if not 0 <= s <= 11:
+        raise ValueError(f"s_patchout_f must lie in [0, 11] (12 frequency rows, at least one is kept), got {s!r}")
+    return s
+
+
+def patchout_rows(rows, s, n_sets):
+    """Injected row sets (tests): `n_sets` lists (the global pass, then one per window) of 12 - s strictly increasing ints in [0, 12)."""
+    rows = [[r for r in rs] for rs in rows]
+    if len(rows) != n_sets:
+        raise ValueError(f"_patchout_rows: {len(rows)} row sets for {n_sets} backbone calls (the global pass + one per window)")
+    for rs in rows:
+        if any(isinstance(r, bool) or not isinstance(r, int) for r in rs):
+            raise TypeError(f"_patchout_rows must hold ints, got {rs!r}")
+        if len(rs) != 12 - s or any(not 0 <= r < 12 for r in rs) or any(a >= b for a, b in zip(rs, rs[1:])):
+            raise ValueError(f"_patchout_rows: expected {12 - s} strictly increasing rows in [0, 12), got {rs!r}")
+    return rows
+
+
 class _Backbone(_Holder):
     """Parameter layout of `PaSST` (src/models/passt/passt.py:392-452)."""
 
-    def __init__(self, dim, depth, lora=None):
+    def __init__(self, dim, depth, lora=None, s_patchout_f=0):
         super().__init__()
+        self.s_patchout_f = s_patchout_f    # (read at every forward, as in the reference; deepcopy carries it to the EMA teacher)
         self.patch_embed = _PatchEmbed(dim)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, dim))
         self.dist_token = nn.Parameter(torch.zeros(1, 1, dim))
@@ -339,7 +363,11 @@ class PaSST_SED(SEDModel):
             if lora_config is not None: unsupported.append("LoRA")
         if decoder not in (("transformerXL",) if _pmam else ("transformerXL", "conformer")):
             unsupported.append(f"decoder={decoder!r}" + (" (the conformer decoder exists for PaSST_SED only)" if decoder == "conformer" else ""))
-        if s_patchout_f or s_patchout_t: unsupported.append("patchout")
+        if _pmam:
+            if s_patchout_f or s_patchout_t: unsupported.append("patchout")
+        else:
+            patchout_f(s_patchout_f)
+            if s_patchout_t: unsupported.append("s_patchout_t (the reference asserts it off: passt_sed.py:77)")
         if interpolate_mode != "linear": unsupported.append(f"interpolate_mode={interpolate_mode!r}")
         if unsupported:
             raise NotImplementedError("the HIP MAT-SED path covers the MAT-SED configs only; unsupported: "
@@ -354,7 +382,7 @@ class PaSST_SED(SEDModel):
             lora = dict(r=lora_config["r"], lora_alpha=lora_config.get("lora_alpha", 1),
                         requires_grad_pretrain=lora_config.get("requires_grad_pretrain", False))
             self.lora_r, self.lora_scaling = lora["r"], lora["lora_alpha"] / lora["r"]
-        self.backbone = _Backbone(embed_dim, encoder_depth, lora)
+        self.backbone = _Backbone(embed_dim, encoder_depth, lora, s_patchout_f)
         if load_pretrained_model:
             sd = torch.load("./pretrained_model/passt-s-f128-p16-s10-ap.476-swa.pt", map_location="cpu")
             self.backbone.load_state_dict(sd, strict=False)
@@ -393,6 +421,9 @@ class PaSST_SED(SEDModel):
         self.engine = None
         self._mlm_draws = None       # tests may inject {"noise","probs","rand_idx"}
         self._win_toffsets = None    # tests may inject the train-mode window offsets
+        self._patchout_rows = None   # ... and the train-mode kept frequency rows: the global pass's set, then one per window
+        self._pmam = bool(_pmam)
+        self._pending_draws = None   # (toffsets, rows) drawn ahead of the forward that uses them: `predraw`
         self.mask_effective_override = None
         self._index_params()
 
@@ -462,6 +493,38 @@ class PaSST_SED(SEDModel):
         self._last_mask_effective = eff
         return dict(mask_ids=ids, action=action, src_idx=src, effective=eff)
 
+    # ------------------------------------------------------------------ train-mode draws of one forward (needs no GPU)
+    def _train_draws(self, T, encoder_win=False, win_param=(512, 49)):
+        """-> (toffsets, rows) of one forward over T mel frames, either None when the engine's default (offset 0 / all 12 rows) applies.
+        Every backbone call of the reference in training mode draws, on the CPU default generator, a time-position offset
+        `randint(1 + 99 - tp)` when its tp < 99 patches are fewer than the table (passt.py:504-509), then -- with s_patchout_f -- the
+        kept rows `randperm(12)[:12 - s].sort()` (passt.py:537).  The global pass comes first (99 patches: no offset), then the windows
+        in sweep order.  Eval mode draws nothing and drops nothing; injected values replace the draws they stand for."""
+        s = patchout_f(self.backbone.s_patchout_f)
+        if s and self._pmam:
+            raise NotImplementedError("the HIP MAT-SED path covers the MAT-SED configs only; unsupported: patchout")
+        starts = window_starts(T, win_param[0], win_param[1]) if encoder_win else []
+        toffsets = list(self._win_toffsets) if (encoder_win and self._win_toffsets is not None) else None
+        if not self.training:
+            return toffsets, None
+        rows = patchout_rows(self._patchout_rows, s, 1 + len(starts)) if (s and self._patchout_rows is not None) else None
+        draw_off, draw_rows = encoder_win and toffsets is None, bool(s) and rows is None
+        draw = lambda: torch.randperm(12)[:12 - s].sort().values.tolist()
+        if draw_off: toffsets = []
+        if draw_rows: rows = [draw()]
+        for left in starts:
+            tpw = (min(left + win_param[0], T) - left - 16) // 10 + 1
+            if draw_off:
+                toffsets.append(int(torch.randint(1 + 99 - tpw, (1,)).item()) if tpw < 99 else 0)
+            if draw_rows:
+                rows.append(draw())
+        return toffsets, rows
+
+    def predraw(self, T, encoder_win=False, win_param=(512, 49)):
+        """Make the train-mode draws of the NEXT forward now.  For a caller that issues another model's forward first although the
+        reference runs this one first (the trainer's teacher on its side stream): the draw order stays the reference's."""
+        self._pending_draws = self._train_draws(T, bool(encoder_win), win_param)
+
     # ------------------------------------------------------------------ forward (passt_sed.py:242-296)
     def forward(self, input, encoder_win=False, mix_rate=0.5, win_param=[512, 49], temp_w=1, pad_mask=None):
         if not input.is_cuda:
@@ -472,16 +535,12 @@ class PaSST_SED(SEDModel):
         B, _, T = input.shape
         kw = dict(encoder_win=bool(encoder_win), mix_rate=float(mix_rate), win_param=tuple(win_param),
                   temp_w=float(temp_w), pad_mask=pad_mask)
-        if encoder_win:
-            starts = window_starts(T, win_param[0], win_param[1])
-            if self._win_toffsets is not None:
-                kw["toffsets"] = list(self._win_toffsets)
-            elif self.training:  # passt.py:504-509: one random time-pos offset per (short) window pass
-                offs = []
-                for left in starts:
-                    tpw = (min(left + win_param[0], T) - left - 16) // 10 + 1
-                    offs.append(int(torch.randint(1 + 99 - tpw, (1,)).item()) if tpw < 99 else 0)
-                kw["toffsets"] = offs
+        pending, self._pending_draws = getattr(self, "_pending_draws", None), None
+        toffsets, rows = pending if pending is not None else self._train_draws(T, bool(encoder_win), win_param)
+        if toffsets is not None:
+            kw["toffsets"] = toffsets
+        if rows is not None:
+            kw["rows"] = rows
         self._last_mask_effective = False
         if self.mlm:
             kw["mlm_plan"] = self._mlm_plan(B, (99 + 1) * self.decode_ratio, input.device, encoder_win)

@@ -451,6 +451,9 @@ class MatSedTrainer:
             if self._side is None:
                 self._side = torch.cuda.Stream()
             self._side.wait_stream(main)
+            # (the reference runs the student first: its train-mode draws -- patchout rows, window offsets -- come before the teacher's)
+            sk = kw["train_stu_kwargs"]
+            self.net.predraw(stu_feat.shape[-1], sk.get("encoder_win", False), sk.get("win_param", (512, 49)))
             with torch.cuda.stream(self._side), torch.no_grad():
                 tch_strong, tch_weak, tch_other = self.ema_net(tch_feat, **kw["train_tch_kwargs"])
             stu_strong, stu_weak, stu_other = self.net(stu_feat, **kw["train_stu_kwargs"])
