@@ -314,11 +314,16 @@ int sed_fpool_rows_bwd(const float* dpooled, const float* x, const float* mean, 
 /* InterpolateModule linear x ratio (+ replicated last frame) (passt_sed.py:13-34,258-259) */
 int sed_interp_fwd(const float* in, float* out, int B, int tin, int pad, int ratio, hipStream_t stream);
 int sed_interp_bwd(const float* dout, float* din, int B, int tin, int pad, int ratio, hipStream_t stream);
-/* EncoderSlideWindow merge + global/local mix (src/models/encoder_slide_window.py:16-36; passt_sed.py:266-271) */
+/* EncoderSlideWindow merge + global/local mix (src/models/encoder_slide_window.py:16-36; passt_sed.py:266-271).
+   Window w (0..nW-1) starts at output frame lefts[w] and holds tps[w] pooled frames per clip; its [B, tps[w], 768] block begins at row
+   offs[w] of pooled_win.  The row ranges [offs[w], offs[w] + B tps[w]) are disjoint and tile [0, rows), rows = B sum_w tps[w]; they
+   may lie in ANY order (offs need not grow with w).  Output frames of a window at or past T are dropped, frames no window covers
+   get a local part of 0. */
 int sed_window_mix(const float* pooled_win, const int* lefts, const int* tps, const int* offs, int nW, float* x,
                    float mix, int B, int T, int ratio, hipStream_t stream);
 /* its backward (autograd of encoder_slide_window.py:16-36 + the mix of passt_sed.py:266-271, student with encoder_win=True):
-   dx [B, T, 768] -> dpooled_win (same packed layout as pooled_win, `rows` rows in all) and dglobal = (1 - mix) dx */
+   dx [B, T, 768] -> dpooled_win (same packed layout and the same lefts / tps / offs tables as pooled_win, `rows` rows in all, every
+   one of them written) and dglobal = (1 - mix) dx */
 int sed_window_mix_bwd(const float* dx, const int* lefts, const int* tps, const int* offs, int nW, float* dpooled_win,
                        float* dglobal, float mix, int B, int T, int ratio, int rows, hipStream_t stream);
 /* MlmModule.setence_mask application (src/models/transformer/mask.py:62-85) and masked MSE (mlm_passt/train.py:36-38) */

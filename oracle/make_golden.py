@@ -875,6 +875,34 @@ def gen_winbwd():
     save(tag, **out)
 
 
+def gen_winbwd31():
+    """`gen_winbwd` on a RAGGED window set: win_param [512, 31] gives 16 windows of 50 time patches and a last one of 49 (488 frames,
+    encoder_slide_window.py:28), and leaves the output frames 986..999 uncovered -- two window groups in the HIP engine, the gradient of
+    the shorter one through its own slices and GEMM shapes.  Same model, same input and the same loss as `gen_winbwd` (its mel and its
+    loss weights, drawn under ITS tag: weights drawn under a tag of their own happened to sum the 20 000 posteriors to -0.94, a
+    near-total cancellation against which a relative loss error says nothing), same digest format; 17 recorded offsets."""
+    tag, src = "model_d768_l2_winbwd31", "model_d768_l2_winbwd"
+    B = 2
+    out = {}
+    mel = torch.from_numpy(synth.det_uniform(f"{src}/mel", (B, 128, 1000), -1.2, 1.2))
+    net = build_reference_model(768, False, 2, 2)
+    net.train()
+    for p in net.parameters():
+        p.requires_grad_(True)
+    torch.manual_seed(59)
+    rec = DrawRecorder()
+    with rec.recording():
+        strong, weak, other = net(mel, encoder_win=True, mix_rate=0.5, win_param=[512, 31], temp_w=1)
+    out["toffsets"] = np.asarray([int(x.item()) for x in rec.of("randint")])
+    assert out["toffsets"].shape == (17,), out["toffsets"].shape
+    loss = _weighted_loss(src, strong, weak, other["at_out"])
+    loss.backward()
+    out["loss"] = t2n(loss)
+    out["strong"] = t2n(strong)
+    _grad_digest(net, out, "")
+    save(tag, **out)
+
+
 def gen_evalpath():
     """Score tables and event lists from the reference's own decode functions (src/codec/decoder.py:15-103) on synthetic
     posteriors.  pandas 2 dropped DataFrame.append and scipy dropped the ndimage.filters namespace the reference still uses:
@@ -1238,7 +1266,7 @@ def gen_val12():
 
 
 GENS = dict(val12=gen_val12, augment2=gen_augment2, trajectory=gen_trajectory, pmamflops=gen_pmamflops, frontend=gen_frontend, augment=gen_augment, micro=gen_micro, full=gen_full, full12=gen_full12,
-            schedule=gen_schedule, postprocess=gen_postprocess, losses=gen_losses, trainstep=gen_trainstep, trainstep12=gen_trainstep12, full12train=gen_full12_train, winbwd=gen_winbwd, evalpath=gen_evalpath, datapipe=gen_datapipe, pmam=gen_pmam, pmamstep=gen_pmamstep, pmamft=gen_pmamft)
+            schedule=gen_schedule, postprocess=gen_postprocess, losses=gen_losses, trainstep=gen_trainstep, trainstep12=gen_trainstep12, full12train=gen_full12_train, winbwd=gen_winbwd, winbwd31=gen_winbwd31, evalpath=gen_evalpath, datapipe=gen_datapipe, pmam=gen_pmam, pmamstep=gen_pmamstep, pmamft=gen_pmamft)
 
 DASM_HEAD = dict(B=2, tdim=5, n_base=8, n_novel=4, qdim=1024, at_layers=2, cnn_t=15)
 

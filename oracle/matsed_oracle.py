@@ -267,22 +267,51 @@ def f_pool_mean(sd, layer_out, f_dim, t_dim):
     return h.reshape(B, f_dim, t_dim, D).mean(dim=1)
 
 
-def interp_linear(x: torch.Tensor, ratio: int = 10) -> torch.Tensor:
+def interp_linear(x: torch.Tensor, ratio: int = 10, fused_index: bool = False) -> torch.Tensor:
     """F.interpolate(mode='linear', align_corners=False, scale_factor=ratio) along dim 1 of [B,T,C],
-    restated in closed form."""
+    restated in closed form.  The source index and `lam` are fp32 whatever x is; the rest runs in x's type.
+    `fused_index`: the index as torch's area_pixel_compute_source_index writes it, scale * (j + 0.5) - 0.5 with scale = float(1 / ratio),
+    evaluated as ONE fused multiply-add -- bit for bit the `src` of interp_coeff in csrc/norm_elem.hip (the quotient form below differs
+    from it by one fp32 ulp of `src` in about a fifth of the frames at ratio 10)."""
     if ratio == 1:
         return x
     T = x.shape[1]
     j = torch.arange(T * ratio, dtype=torch.float32)
-    src = torch.clamp((j + 0.5) / ratio - 0.5, min=0.0)
+    if fused_index:
+        scale = torch.tensor(1.0 / ratio, dtype=torch.float64).float().double()
+        src = torch.clamp((scale * (j.double() + 0.5) - 0.5).float(), min=0.0)    # the product of two fp32 values is exact in float64
+    else:
+        src = torch.clamp((j + 0.5) / ratio - 0.5, min=0.0)
     i0 = src.floor().to(torch.int64)
     i1 = torch.clamp(i0 + 1, max=T - 1)
-    lam = (src - i0.to(torch.float32)).view(1, -1, 1)
+    lam = (src - i0.to(torch.float32)).to(x.dtype).view(1, -1, 1)
     return (1.0 - lam) * x[:, i0] + lam * x[:, i1]
 
 
 def window_starts(n_in=1000, win=512, step=49):
     return list(range(0, n_in + step - win, step))  # encoder_slide_window.py:27
+
+
+def merge_windows(frames, lefts, emb_len, ratio=10, mix=None, x=None, fused_index=False):
+    """The merge of encoder_slide_window.py:29-36 (+ the global / local mix of passt_sed.py:266-271 when `x` is given): window w's
+    pooled frames `frames[w]` [B, tp_w, D] are interpolated x`ratio` and added at output frames lefts[w] ...; what falls at or past
+    `emb_len` is dropped; every output frame is divided by the number of windows that cover it, frames no window covers come out 0
+    (the reference's NaN -> 0).  Runs in the type of `frames` (float64 for the kernel tests) and is differentiable.
+    Returns the local part [B, emb_len, D], or (1 - mix) x + mix local."""
+    B, _, D = frames[0].shape
+    emb = frames[0].new_zeros(B, emb_len, D)
+    acc = frames[0].new_zeros(B, emb_len, D)
+    for fr, o_left in zip(frames, lefts):
+        fr = interp_linear(fr, ratio, fused_index)
+        o_right = int(min(emb_len, o_left + fr.shape[1]))
+        if o_right <= o_left:
+            continue
+        emb[:, o_left:o_right] += fr[:, :o_right - o_left]
+        acc[:, o_left:o_right] += 1
+    emb = torch.where(acc > 0, emb / acc.clamp_min(1), torch.zeros_like(emb))
+    if x is None:
+        return emb
+    return mix * emb + (1 - mix) * x
 
 
 def slide_window_features(sd, mel, win_param=(512, 49), depth=12, feature_layer=10, toffsets=None, ratio=10, pool_fn=None,
@@ -296,21 +325,13 @@ def slide_window_features(sd, mel, win_param=(512, 49), depth=12, feature_layer=
     win, step = win_param
     emb_len = T  # decode_ratio * 100 frames == input frames here
     scale = emb_len / T
-    D = sd["out_norm.weight"].shape[0]
-    emb = torch.zeros(B, emb_len, D)
-    acc = torch.zeros(B, emb_len, D)
+    frames, lefts = [], []
     for wi, left in enumerate(window_starts(T, win, step)):
         right = min(left + win, T)
         enc = encoder_fn(sd, mel[:, :, left:right], depth=depth, toffset=0 if toffsets is None else int(toffsets[wi]))
-        fr = pool_fn(sd, enc["layers"][feature_layer - 1], enc["f_dim"], enc["t_dim"])
-        fr = interp_linear(fr, ratio)
-        o_left = round(left * scale)
-        o_right = int(min(emb_len, o_left + fr.shape[1]))
-        emb[:, o_left:o_right] += fr[:, :o_right - o_left]
-        acc[:, o_left:o_right] += 1
-    emb = emb / acc
-    emb[torch.isnan(emb)] = 0
-    return emb
+        frames.append(pool_fn(sd, enc["layers"][feature_layer - 1], enc["f_dim"], enc["t_dim"]))
+        lefts.append(round(left * scale))
+    return merge_windows(frames, lefts, emb_len, ratio)
 
 
 # =====================================================================================================

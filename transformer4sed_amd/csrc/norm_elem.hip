@@ -487,7 +487,8 @@ extern "C" int sed_fpool_bwd(const float* dpooled, const float* x, const float* 
 // ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void interp_coeff(int j, int ratio, int tlen, int tin, int& i0, int& i1, float& lam) {
     // torch's area_pixel_compute_source_index: scale * (dst + 0.5) - 0.5 with scale = (float)(1.0 / scale_factor)
-    float src = (float)(1.0 / (double)ratio) * ((float)j + 0.5f) - 0.5f;
+    // (one fused multiply-add, written out: tests/window_cases.py restates this rounding)
+    float src = fmaf((float)j + 0.5f, (float)(1.0 / (double)ratio), -0.5f);
     src = src < 0.f ? 0.f : src;
     i0 = (int)src;
     i1 = i0 + 1 < tlen ? i0 + 1 : tlen - 1;
@@ -552,7 +553,7 @@ extern "C" int sed_interp_bwd(const float* dout, float* din, int B, int tin, int
 
 // Sliding-window merge (encoder_slide_window.py:16-36 + passt_sed.py:266-271), windows folded into the batch:
 // window w's pooled frames live at pooled_win + offs[w] * D as [B, tps[w], D] (the last window of a sweep can be one
-// patch shorter than the others);
+// patch shorter than the others); the row ranges [offs[w], offs[w] + B tps[w]) tile the packed buffer, in any order;
 //   x[b, j] = (1 - mix) x[b, j] + mix * (sum_w interp(pooled_w[b])[j - left_w]) / cnt_j
 // (cnt_j == 0 -> local part is 0, the reference's NaN -> 0).
 __global__ void window_mix_kernel(const float* __restrict__ pooled_win, const int* __restrict__ lefts,
@@ -601,8 +602,8 @@ __global__ void window_mix_bwd_kernel(const float* __restrict__ dx, const int* _
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int d4 = (int)(idx % (DM / 4));
         const int row = (int)(idx / (DM / 4));
-        int w = 0;
-        for (int k = 1; k < nW; ++k) w = (row >= offs[k]) ? ((offs[k] >= offs[w]) ? k : w) : w;   // the window whose row range holds `row`
+        int w = 0;   // the window whose row range [offs[w], offs[w] + B tps[w]) holds `row`: the ranges tile [0, rows), in any order
+        for (int k = 0; k < nW; ++k) { const int r = row - offs[k]; w = (r >= 0 && r < B * tps[k]) ? k : w; }
         const int tpw = tps[w], rel = row - offs[w], b = rel / tpw, i = rel - b * tpw, left = lefts[w];
         int jlo = (i - 1) * ratio - ratio, jhi = (i + 1) * ratio + ratio;
         jlo = jlo < 0 ? 0 : jlo;
