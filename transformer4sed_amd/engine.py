@@ -24,6 +24,7 @@ from .ops import EPI_F32, EPI_F32_RESID, EPI_BF16, EPI_GELU, EPI_DGELU, EPI_F32_
 D = 768
 H = 12
 NCLS_MAX = 16
+WCORR_STEP = 8      # `_wcorr_bias`: clip means from every 8th token (1/8 of the extra read)
 
 
 def version_key(sources, form=None):
@@ -134,15 +135,14 @@ class SedEngine:
         # padding written once stays zero and the buffers can be reused step after step instead of being re-zeroed (1.1 ms / step)
         self._zpool = {}
         self._pool_busy = False
-        # 16-bit type of the FORWARD MFMA operands (activations + weight images).  IEEE half (default) keeps the frame
-        # posteriors within 1e-3 of the fp32 reference at the bf16 MFMA rate; gradient-side operands are always bf16.
-        # (round 6: no SED_FWD_DTYPE switch any more -- a bf16 forward misses the 1e-3 posterior bound, so it cannot be a supported mode; the
-        #  kernels stay templated on the type and the kernel tests exercise both)
+        # 16-bit type of the FORWARD MFMA operands (activations + weight images).  IEEE half keeps the frame posteriors within 1e-3 of the
+        # fp32 reference at the bf16 MFMA rate; gradient-side operands are always bf16.  (A bf16 forward misses that bound, so it is not a
+        # mode; the kernels stay templated on the type and the kernel tests exercise both.)
         self.act = F16
         # Context-network (and MLM head) GEMMs in split precision: f16 hi + f16 lo operands, three MFMA products via the
         # concatenated reduction dim.  Their operand rounding is what limits posterior parity: with
-        # it 1e-3 holds with a 10x margin, for ~4 % of step time.  SED_DECODER_SPLIT=0 turns it off.
-        self.split = self.act == F16      # (round 6: the SED_DECODER_SPLIT=0 A/B switch is gone -- without it the posteriors miss 1e-3)
+        # it 1e-3 holds with a 10x margin, for ~4 % of step time; without it the posteriors miss 1e-3.
+        self.split = self.act == F16
         # weight gradients: TN kernel on the operands as they lie (default) or transposed copies + NT split-K kernel
         self.dw_tn = True                 # (attribute kept for tools/trajectory_probe.py's summation-order experiment; no environment switch)
         # weight-gradient (TN) GEMMs on a side stream: they depend only on dY and the saved operand, nothing in the backward chain
@@ -150,70 +150,48 @@ class SedEngine:
         # LayerNorm / cast passes.  Joined before every stage hook and at the end of backward.  Off while the kernel timer
         # instruments a step (interleaved kernels inflate every per-launch duration).
         self.dw_side = os.environ.get("SED_DW_STREAM", "1") != "0"
-        # rel-pos backward: dK / dV from the dS^T / P^T slabs the dQ kernel stores (streaming kernel) instead of recomputing the scores
-        self.relpos_stream = True
+        # No-grad passes that are not scored run their LayerNorms folded into the GEMMs around them (`_encoder_fwd`); between folded
+        # blocks the residual stream lives as two planes, f16 hi + 8-bit lo (6 bytes per element through a producer, the stream to ~2^-19).
+        # SED_LN_FOLD=0 keeps the LayerNorm kernels.
         self.ln_fold = os.environ.get("SED_LN_FOLD", "1") != "0"
-        self.ln_bwd16 = True
-        # folded blocks: residual stream as two planes between producers -- "8" (default): f16 hi + 8-bit lo (6 bytes per element through a
-        # producer, the stream to ~2^-19), "1": f16 hi + f16 lo (8 bytes), "0": fp32 stream + f16 image (10 bytes)
-        # (round 6: fixed at the byte-plane form; the f16-plane and fp32-stream forms stay reachable through these attributes for the kernel tests)
-        self.ln_lo8 = True
-        self.ln_planes = True
-        self.ln_dual = True      # bf16 copies of the saved LayerNorm outputs for the weight gradients
         # Context-network GEMMs that do not need all three split-precision terms (tools/err_sim.py SIM_DEC_TERMS=1: logit error of the whole
         # decoder 3.96e-4 with three terms everywhere): in_proj without the activation's lo part (5.4e-4; the weight's lo part is the one that
         # matters there: 1.9e-3 without it) -> two K passes instead of three on the largest decoder GEMM, and its LayerNorm writes a plain f16
-        # image; linear_pos on plain f16 operands (5.3e-4).  out_proj / fc1 / fc2 keep three terms.  SED_DEC_TERMS=3 restores three everywhere.
+        # image; linear_pos on plain f16 operands (5.3e-4).  out_proj / fc1 / fc2 keep three terms.
         self.dec_terms2 = True
         self._genc16 = None
         self._dw_stream = None
         self._dw_pending = False
         # Evaluation-mode encoder.  The f16 weight images are the largest single term of the posterior error (tools/err_sim.py: logit
         # error 1.6e-3 of 2.0e-3 in total), so passes whose posteriors are SCORED (module in eval mode: validation, test, inference)
-        # do not round the weights:
-        #   exact (default)  two-term weights [f16(W) | f16(W - f16(W))], the activation panel walked twice (sed_gemm_*_w2): the fp32
-        #                    weight to ~2^-19 for twice the encoder GEMM work of an inference pass;
-        #   (inside it)      f16 weights + mean_t(x) . (W - f16(W))^T per clip as a row-group bias (`_wcorr_bias`): the part of the rounding
-        #                    that is common to all tokens of a clip, ~2 % of an inference pass, about a third of the gain -- used for fc1 and
-        #                    for inputs below the 256^2 kernel's domain;
-        #   0                off.
-        # Training-mode passes (student, and the teacher inside the train step) never pay for it; SED_ENC_WCORR_ALL=1 extends it to
-        # every no-grad pass.
-        # (round 3 shipped the per-clip mean correction as a selectable whole-encoder mode -- 9.3e-4 of the 1e-3 bound on the validation
-        #  configuration, no margin -- and "0" (plain f16 weights, 1.2e-3) as a switch; neither meets the bound, so since round 6 there is no
-        #  SED_ENC_WCORR environment variable: scored passes always run `exact`.  The attribute stays for tools/err_sim.py.)
-        self.wcorr = "exact" if self.act == F16 else "0"
-        # The lo product of the exact mode, x . (W - f16(W))^T, is 2^-12 of the result: it can run on the fp8 matrix path (e4m3 images of both
+        # do not round the weights; training-mode passes (student, and the teacher inside the train step) never pay for it.  Per GEMM:
+        #   w2    two-term weights [f16(W) | f16(W - f16(W))], the activation panel walked twice (sed_gemm_*_w2): the fp32 weight to ~2^-19
+        #         for twice the GEMM work -- qkv, proj and fc2;
+        #   gb    f16 weights + mean_t(x) . (W - f16(W))^T per clip as a row-group bias (`_wcorr_bias`): the part of the rounding that is
+        #         common to all tokens of a clip, ~2 % of an inference pass, about a third of the gain -- fc1 (the weight whose rounding
+        #         matters least, and a third of the encoder's GEMM work), and every GEMM of an input below the 256^2 kernel's domain.
+        # The lo product of w2, x . (W - f16(W))^T, is 2^-12 of the result: it can run on the fp8 matrix path (w2f8: e4m3 images of both
         # factors, v_mfma_scale_f32_16x16x128_f8f6f4: half of an f16 K pass; csrc/gemm.hip GemmArgs.k8).  The activations' e4m3 images come
         # out of the producing kernels (LayerNorm, attention, fc1's epilogue) in the same rows as the f16 values.  e4m3 keeps ~5 % of the lo
         # product as error, which is not free here (every posterior of the validation configuration sits within 15 % of its bound), so the
-        # default takes only the GEMM that pays for it with margin to spare on BOTH fixtures: fc2.  Measured on the validation step (clips/s;
-        # worst posterior of the val12 fixture, bound 7e-4; depth-2 fixture at temp 0.5, bound 1e-3):  f16 138.9 / 5.96e-4 / 6.3e-4;
-        # fc2 141.6 / 5.5e-4 / 7.6e-4 (default);  proj,fc2 143.7 / 6.3e-4 / 6.8e-4;  qkv,fc2 146.7 / 6.2e-4 / 9.2e-4 (round 5's default: 8 %
-        # under the 1e-3 specification on synthetic weights -- e4m3 flushes |x| / 4 < 2^-9 and clamps at 1792, a checkpoint with louder
-        # channels can cross it unseen, so qkv is opt-in: SED_ENC_W2=f8:qkv,fc2);  qkv,proj 145.1 / 6.9e-4 / 9.0e-4;
-        # qkv,proj,fc2 146.9 / 6.8e-4 / 1.02e-3 (over the second bound: proj gains 36 us per launch and its image costs the attention as much).
-        # SED_ENC_W2=f16: both products in f16 (the round-3 / round-4 form); f8:<subset of qkv,proj,fc2>: that subset.
+        # default takes only the GEMM that pays for it with margin to spare on both fixtures: fc2 (DESIGN.md section 2 has the measured
+        # speed and error of every subset; qkv is opt-in because e4m3 flushes |x| / 4 < 2^-9 and clamps at 1792 -- a checkpoint with louder
+        # channels than the synthetic weights can cross the bound unseen).
+        # SED_ENC_W2=f16: both products in f16; f8:<subset of qkv,proj,fc2>: that subset on the fp8 path.
         mode = os.environ.get("SED_ENC_W2", "f8")
         head, _, which = mode.partition(":")
         self.w2_f8_set = frozenset(w for w in (which.split(",") if which else ("fc2",)) if w)
         if head not in ("f8", "f16") or (head == "f16" and which) or not self.w2_f8_set <= {"qkv", "proj", "fc2"}:
             raise ValueError(f"SED_ENC_W2={mode!r}: expected f16, f8, or f8:<subset of qkv,proj,fc2>")
         self.w2_f8 = head == "f8"
-        self.wcorr_all = False       # (attribute: extend the evaluation-mode weights to every no-grad pass; tools/err_sim experiments)
-        # fc1 inside the exact mode: its rounding matters least of the four weights (tools/err_sim.py) and it is a third of the encoder's
-        # GEMM work -- f16 weights + the per-clip mean correction there (default) keep the posteriors where the all-two-term form has them
-        # (worst fixture 6.8e-4 vs 7.2e-4) for 7 % less validation time.  SED_ENC_WCORR_FC1=1: two-term fc1 too; =0: plain f16 fc1.
-        self.wcorr_fc1 = False
-        self.wcorr_fc1_mean = True
-        self.wcorr_step = 8     # mean: clip means from every 8th token (1/8 of the extra read)
 
     def _wcorr_on(self, save):
-        if self.wcorr == "0" or save:
+        """Does this pass run the evaluation-mode encoder weights?"""
+        if self.act != F16 or save:
             return False
         if getattr(self.m, "lora_r", 0) and not getattr(self.m, "lora_merged", False):
             return False        # PaSST_CNN in train mode: the GEMM operand is W + s B A, not the master the residual image is taken from
-        return self.wcorr_all or not self.m.training
+        return not self.m.training
 
     def _lnf_image(self, W, wname, bname, gname, btname):
         """(f16(gamma (.) W), colS, colC) of a Linear that follows a LayerNorm (sed_ln_fold_weight), cached per weight on all four
@@ -257,7 +235,7 @@ class SedEngine:
         wlo = self._wlo_image(W, name)
         K = wlo.shape[1]
         mean = torch.empty(groups, K, dtype=x16.dtype, device=x16.device)
-        call("sed_group_colmean_ld", x16, mean, groups, rows, K, ld or x16.shape[-1], self.wcorr_step, is_f16(x16))
+        call("sed_group_colmean_ld", x16, mean, groups, rows, K, ld or x16.shape[-1], WCORR_STEP, is_f16(x16))
         out = torch.empty(groups, wlo.shape[0], dtype=F32, device=x16.device)
         gemm_nt(mean, wlo, EPI_F32, outF=out, alpha=1.0 / 2048.0)
         return out
@@ -385,24 +363,44 @@ class SedEngine:
                  x[s * B:(s + 1) * B], B, tp)
         if save:
             ctx["cols"] = cols
-        # per-call scratch (reused across layers when not saving)
-        # tensors that only the backward reads (GELU pre-activation) are produced as bf16 right away
         # Blocks below the lowest one with a trainable tensor are never walked by the backward (frozen encoder of the pretrain / finetune1
         # stages, `freeze_layer`): they run like a no-grad pass -- nothing saved, in place, LayerNorms folded -- even inside a pass that saves.
         lo_f = self._lowest_trainable_fwd(m.depth) if save else m.depth
         # q, k, v stay row-major: the attention forward and backward take every transposed operand out of their LDS tiles
         # (ds_read_b64_tr_b16); the backward makes the bf16 images of the saved f16 Q / K / V tiles on the way into LDS
         mk_qkv = lambda: [E(Bx * H, N, 64, dt=A16), E(Bx * H, N, 64, dt=A16), E(Bx * H, N, 64, dt=A16)]
-        scratch = None
+        scratch = None          # per-call scratch (reused across layers when not saving)
         pooled = None
+        # Form of each linear site in this pass (the constructor's comment on the evaluation-mode encoder): "f16" plain weights (training,
+        # saving blocks, N < 128), "gb" f16 weights + the per-clip mean correction, "w2" two-term weights, "w2f8" two-term weights with the
+        # lo product on the fp8 path.  fc1 never goes beyond gb; inputs below the 256^2 kernel's domain (M < 1024) run gb everywhere.
         wc = self._wcorr_on(save) and N >= 128
-        w2 = wc and self.wcorr == "exact" and M >= 1024      # (the 256^2 kernel's domain; tiny inputs take the mean correction)
-        w2f8 = w2 and self.w2_f8 and f16 == 1
-        # which of the two-term GEMMs take their lo product on the fp8 path (fc1: when it is two-term at all, SED_ENC_WCORR_FC1=1); the
-        # operand rows of those are [f16 | e4m3] -- pitch 3 D / 2
-        q8, p8, f28 = (w2f8 and "qkv" in self.w2_f8_set), (w2f8 and "proj" in self.w2_f8_set), (w2f8 and "fc2" in self.w2_f8_set)
-        f18 = w2f8 and not self.wcorr_fc1_mean and self.wcorr_fc1
+        w2 = wc and M >= 1024
+        w2f8 = w2 and self.w2_f8
+
+        def form_of(site):
+            if not wc:
+                return "f16"
+            if not w2 or site == "fc1":
+                return "gb"
+            return "w2f8" if w2f8 and site in self.w2_f8_set else "w2"
+        f_qkv, f_proj, f_fc1, f_fc2 = form_of("qkv"), form_of("proj"), form_of("fc1"), form_of("fc2")
+        # the operand rows of a w2f8 GEMM are [f16 | e4m3], written by the producing kernel -- pitch 3 D / 2
+        q8, p8, f28 = f_qkv == "w2f8", f_proj == "w2f8", f_fc2 == "w2f8"
         pitch = lambda on: D + D // 2 if on else D
+
+        def linear(p, site, form, xin, epi, K, **out):
+            """The proj / fc1 / fc2 GEMM of block `p` in its form"""
+            wn, b = p + site + ".weight", self.P(p + site + ".bias")
+            if form == "w2f8":
+                img, s = self._w2f8_image(W, wn)
+                gemm_nt_w2f8(xin, img, s, epi, K, bias=b, **out)
+            elif form == "w2":
+                gemm_nt(xin, self._w2_image(W, wn), epi, bias=b, two_term=True, **out)
+            elif form == "gb":
+                gemm_nt(xin, W[wn].w, epi, bias=b, gbias=self._wcorr_bias(W, wn, xin, Bx, N), gb_rows=N, **out)
+            else:
+                gemm_nt(xin, W[wn].w, epi, bias=b, **out)
         # No-grad f16 passes that are not scored (the teacher inside the train step, frozen encoders): LayerNorm folded into the GEMMs around
         # it -- the residual GEMM writes the f16 image of the new stream + per-row partial sums, the next GEMM consumes the RAW image against
         # gamma-scaled weights and normalises in its epilogue (csrc/gemm.hip, GemmArgs.rowpart / rowstat).  Two passes over the stream less
@@ -410,29 +408,26 @@ class SedEngine:
         fold_ok = self.ln_fold and not wc and self.act == F16 and M >= 1024 and not getattr(m, "lora_r", 0) and (not save or lo_f > 0)
         have_stat = False       # statistics of the current stream available (false before the first residual GEMM)
         if fold_ok:
-            # between folded blocks the residual stream lives as two f16 planes (x16f = hi, which is also the consumers' A operand, + xlo)
-            # instead of fp32: a producer then moves 8 bytes per element instead of 10 (csrc/gemm.hip, GemmArgs.res_lo / out_lo)
+            # between folded blocks the residual stream lives as two planes (x16f = f16 hi, which is also the consumers' A operand, + xlo:
+            # 8-bit lo) instead of fp32: a producer then moves 6 bytes per element instead of 10 (csrc/gemm.hip, GemmArgs.res_lo / out_lo)
             # (slab-major planes are addressed through one 32-bit buffer range: a plane has to stay below 2 GiB -- M < 1.4 M tokens for the
             #  stream planes, M < 349 k for the fc1 activation; beyond that the f16 planes / the row-major activation)
-            lo8 = self.ln_lo8 and M * D * 2 < 2 ** 31
-            slab_ok = lo8
+            lo8 = M * D * 2 < 2 ** 31
             x16f, xlo, partf, statf = E(M, D, dt=F16), E(M, D, dt=torch.uint8 if lo8 else F16), E(M, D // 64, 2), E(M, 2)
             lnp = "sed_gemm_nt_lnp8" if lo8 else "sed_gemm_nt_lnp"      # (lnp8: both planes slab-major, read back by the *_lnc8 consumers)
             qkv_lnc, nt_lnc = ("sed_gemm_qkv_lnc8", "sed_gemm_nt_lnc8") if lo8 else ("sed_gemm_qkv_lnc", "sed_gemm_nt_lnc")
         planes = False              # the current stream value is in (x16f, xlo) rather than in the fp32 tensor
         for li in range(m.depth):
             p = f"backbone.blocks.{li}."
-            L = {}
             sv = save and li >= lo_f          # this block's activations are read by a backward
             fold = fold_ok and not sv
-            B16 = BF16 if sv else A16
             if sv or scratch is None:
                 h16 = E(M, pitch(q8), dt=A16)
                 q, k, v = mk_qkv()
                 o16 = E(M, pitch(p8), dt=A16)
                 lse = E(Bx * H, N)
-                h2 = E(M, pitch(f18), dt=A16)
-                hpre = E(M, 4 * D, dt=B16) if not w2f8 else None
+                h2 = E(M, D, dt=A16)
+                hpre = E(M, 4 * D, dt=BF16) if sv else None       # (GELU pre-activation: only the backward reads it, so bf16 right away)
                 act = E(M, 4 * pitch(f28), dt=A16)
                 mean1, rstd1, mean2, rstd2 = (E(M), E(M), E(M), E(M)) if sv else (None, None, None, None)
                 scratch = (h16, q, k, v, o16, lse, h2, hpre, act)
@@ -442,7 +437,7 @@ class SedEngine:
             x_in = x
             # Saving blocks of an f16 pass: the LayerNorm writes its result twice -- f16 for the forward GEMM, bf16 for the backward's weight
             # gradient, which otherwise converts the saved f16 fragments in registers (17-20 % of that launch).  The f16 tensors are not kept.
-            dual = sv and f16 == 1 and self.ln_dual and not getattr(m, "lora_r", 0)      # (LoRA factors take their gradients from the f16 operand)
+            dual = sv and f16 == 1 and not getattr(m, "lora_r", 0)      # (LoRA factors take their gradients from the f16 operand)
             h16s = h2s = None
             if dual:
                 h16s, h2s = E(M, D, dt=BF16), E(M, D, dt=BF16)
@@ -450,156 +445,60 @@ class SedEngine:
             elif not (fold and have_stat):
                 call("sed_layernorm_fwd", x_in, self.P(p + "norm1.weight"), self.P(p + "norm1.bias"), 1e-6, 1.0, h16, None,
                      mean1, rstd1, M, D, 8 if q8 else f16)
+            wq, bq = p + "attn.qkv.weight", self.P(p + "attn.qkv.bias")
             if fold:
                 last = li + 1 == m.depth or (li + 1 == m.passt_feature_layer and not want_frame) or (save and li + 1 >= lo_f)
                 if have_stat:
-                    wq, sq, cq = self._lnf_image(W, p + "attn.qkv.weight", p + "attn.qkv.bias", p + "norm1.weight", p + "norm1.bias")
-                    call(qkv_lnc, x16f, wq, cq, sq, statf, M, D, H, N, Npad, q, k, v)
+                    wf, sq, cq = self._lnf_image(W, wq, p + "attn.qkv.bias", p + "norm1.weight", p + "norm1.bias")
+                    call(qkv_lnc, x16f, wf, cq, sq, statf, M, D, H, N, Npad, q, k, v)
                 else:       # first block: its LayerNorm ran above (the stream comes from the token assembly, not from a GEMM)
-                    call("sed_gemm_qkv", h16, W[p + "attn.qkv.weight"].w, self.P(p + "attn.qkv.bias"), M, D, H, N, Npad, q, k,
-                         v, None, None, None, None, None, None, None, f16)
-                sp = self.ln_planes
+                    call("sed_gemm_qkv", h16, W[wq].w, bq, M, D, H, N, Npad, q, k, v, None, None, None, None, None, None, None, f16)
                 # (byte-plane runs: the attention output goes head-major = slab-major into the proj GEMM's A operand)
-                slab_o = slab_ok
-                call("sed_mhsa_fwd", q, k, v, o16, lse, Bx, H, N, Npad, f16 | (2 if slab_o else 0))
-                call(lnp, o16, W[p + "attn.proj.weight"].w, M, D, D, 64 if slab_o else D, D, self.P(p + "attn.proj.bias"),
-                     None if planes else x_in, x16f if planes else None, xlo if planes else None,
-                     None if sp else x_in, x16f, xlo if sp else None, partf, D)
-                planes = sp
+                call("sed_mhsa_fwd", q, k, v, o16, lse, Bx, H, N, Npad, f16 | (2 if lo8 else 0))
+                call(lnp, o16, W[p + "attn.proj.weight"].w, M, D, D, 64 if lo8 else D, D, self.P(p + "attn.proj.bias"),
+                     None if planes else x_in, x16f if planes else None, xlo if planes else None, None, x16f, xlo, partf, D)
                 call("sed_ln_fold_stats", partf, statf, M, D // 64, D, 1e-6)
                 w1, s1, c1 = self._lnf_image(W, p + "mlp.fc1.weight", p + "mlp.fc1.bias", p + "norm2.weight", p + "norm2.bias")
                 # (byte-plane runs: the fc1 activation goes slab-major from fc1's epilogue into fc2's A operand -- ldc / lda = 64)
-                slab_act = slab_ok and sp and not (last and not planes) and M * 4 * D * 2 < 2 ** 31
+                slab_act = lo8 and M * 4 * D * 2 < 2 ** 31
                 call(nt_lnc, x16f, w1, M, 4 * D, D, D, D, c1, s1, statf, act, 64 if slab_act else 4 * D)
                 # the block's output has an fp32 reader (f_pool, the final norm, a saving block) -> fp32 out; otherwise it stays in planes
-                f32_out = last or li + 1 == m.passt_feature_layer or not sp
-                if last and not planes:
-                    gemm_nt(act, W[p + "mlp.fc2.weight"].w, EPI_F32_RESID, bias=self.P(p + "mlp.fc2.bias"), res=x_in, outF=x_in)
-                else:
-                    call(lnp, act, W[p + "mlp.fc2.weight"].w, M, D, 4 * D, 64 if slab_act else 4 * D, 4 * D, self.P(p + "mlp.fc2.bias"),
-                         None if planes else x_in, x16f if planes else None, xlo if planes else None,
-                         x_in if f32_out else None, x16f, None if f32_out else xlo, partf, D)
-                    planes = not f32_out
-                    if not last:
-                        call("sed_ln_fold_stats", partf, statf, M, D // 64, D, 1e-6)
-                        have_stat = True
-                x = x_in
-                if li + 1 == m.passt_feature_layer:
-                    pooled = self._fpool_fwd(W, x, Bx, tp, save, ctx)
-                    if not want_frame:
-                        break
-                    if save:
-                        x = x.clone()       # f_pool's backward reads the tensor it was given; the blocks above keep updating in place
-                if save:
-                    ctx["layers"].append(None)
-                continue
-            if w2f8:    # evaluation mode, lo products on the fp8 matrix path: operand rows [f16 | e4m3], written by the producing kernels
-                bq, bp_, b1_, b2_ = (self.P(p + n) for n in ("attn.qkv.bias", "attn.proj.bias", "mlp.fc1.bias", "mlp.fc2.bias"))
-                if q8:
-                    wq, sq = self._w2f8_image(W, p + "attn.qkv.weight")
-                    call("sed_gemm_qkv_w2f8", h16, wq, bq, M, D, H, N, Npad, q, k, v, sq)
-                else:
-                    call("sed_gemm_qkv_w2", h16, self._w2_image(W, p + "attn.qkv.weight"), bq, M, D, H, N, Npad, q, k, v, f16)
-                call("sed_mhsa_fwd", q, k, v, o16, lse, Bx, H, N, Npad, 1 | (4 if p8 else 0))
-                if p8:
-                    wp, sp_ = self._w2f8_image(W, p + "attn.proj.weight")
-                    gemm_nt_w2f8(o16, wp, sp_, EPI_F32_RESID, D, bias=bp_, res=x_in, outF=x_in)
-                else:
-                    gemm_nt(o16, self._w2_image(W, p + "attn.proj.weight"), EPI_F32_RESID, bias=bp_, res=x_in, outF=x_in, two_term=True)
-                call("sed_layernorm_fwd", x_in, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-6, 1.0, h2, None,
-                     mean2, rstd2, M, D, 8 if f18 else f16)
-                if f18:
-                    w1_, s1_ = self._w2f8_image(W, p + "mlp.fc1.weight")
-                    gemm_nt_w2f8(h2, w1_, s1_, EPI_GELU, D, bias=b1_, outH2=act, out_e4m3=bool(f28))
-                elif self.wcorr_fc1:
-                    gemm_nt(h2, self._w2_image(W, p + "mlp.fc1.weight"), EPI_GELU, bias=b1_, outH=None, outH2=act, two_term=True,
-                            ldc=4 * pitch(f28))
-                    if f28:
-                        call("sed_fp8_tail", act, M, 4 * D, 4 * pitch(f28))
-                else:       # fc1 (the weight whose rounding matters least) on f16 weights (+ the per-clip mean correction, default)
-                    gb = self._wcorr_bias(W, p + "mlp.fc1.weight", h2, Bx, N) if self.wcorr_fc1_mean else None
-                    if f28:
-                        call("sed_gemm_nt_gb_e4m3", h2, W[p + "mlp.fc1.weight"].w, M, 4 * D, D, D, D, b1_, act, 4 * pitch(f28),
-                             gb if gb is not None else self._zeros("gb0", (Bx, 4 * D), F32, dev), N)
-                    elif gb is not None:
-                        gemm_nt(h2, W[p + "mlp.fc1.weight"].w, EPI_GELU, bias=b1_, outH=None, outH2=act, gbias=gb, gb_rows=N)
-                    else:
-                        gemm_nt(h2, W[p + "mlp.fc1.weight"].w, EPI_GELU, bias=b1_, outH=None, outH2=act)
-                if f28:
-                    w2_, s2_ = self._w2f8_image(W, p + "mlp.fc2.weight")
-                    gemm_nt_w2f8(act, w2_, s2_, EPI_F32_RESID, 4 * D, bias=b2_, res=x_in, outF=x_in)
-                else:
-                    gemm_nt(act, self._w2_image(W, p + "mlp.fc2.weight"), EPI_F32_RESID, bias=b2_, res=x_in, outF=x_in, two_term=True)
-                x = x_in
-                if li + 1 == m.passt_feature_layer:
-                    pooled = self._fpool_fwd(W, x, Bx, tp, save, ctx)
-                    if not want_frame:
-                        break
-                continue
-            if w2:      # evaluation mode: every encoder GEMM against the two-term weight image
-                call("sed_gemm_qkv_w2", h16, self._w2_image(W, p + "attn.qkv.weight"), self.P(p + "attn.qkv.bias"), M, D, H, N, Npad, q, k, v, f16)
-                call("sed_mhsa_fwd", q, k, v, o16, lse, Bx, H, N, Npad, f16)
-                gemm_nt(o16, self._w2_image(W, p + "attn.proj.weight"), EPI_F32_RESID, bias=self.P(p + "attn.proj.bias"), res=x_in, outF=x_in,
-                        two_term=True)
-                call("sed_layernorm_fwd", x_in, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-6, 1.0, h2, None,
-                     mean2, rstd2, M, D, f16)
-                if self.wcorr_fc1:
-                    gemm_nt(h2, self._w2_image(W, p + "mlp.fc1.weight"), EPI_GELU, bias=self.P(p + "mlp.fc1.bias"), outH=None, outH2=act,
-                            two_term=True)
-                elif self.wcorr_fc1_mean:      # fc1 (the weight whose rounding matters least) on f16 weights + the per-clip mean correction
-                    gemm_nt(h2, W[p + "mlp.fc1.weight"].w, EPI_GELU, bias=self.P(p + "mlp.fc1.bias"), outH=None, outH2=act,
-                            gbias=self._wcorr_bias(W, p + "mlp.fc1.weight", h2, Bx, N), gb_rows=N)
-                else:
-                    gemm_nt(h2, W[p + "mlp.fc1.weight"].w, EPI_GELU, bias=self.P(p + "mlp.fc1.bias"), outH=None, outH2=act)
-                gemm_nt(act, self._w2_image(W, p + "mlp.fc2.weight"), EPI_F32_RESID, bias=self.P(p + "mlp.fc2.bias"), res=x_in, outF=x_in,
-                        two_term=True)
-                x = x_in
-                if li + 1 == m.passt_feature_layer:
-                    pooled = self._fpool_fwd(W, x, Bx, tp, save, ctx)
-                    if not want_frame:
-                        break
-                continue
-            if wc:      # (mean mode) every GEMM carries its per-clip weight-rounding correction as a row-group bias
-                gb = lambda nm, xin: self._wcorr_bias(W, p + nm, xin, Bx, N)
-                call("sed_gemm_qkv_gb", h16, W[p + "attn.qkv.weight"].w, self.P(p + "attn.qkv.bias"), M, D, H, N, Npad, q, k, v, f16,
-                     gb("attn.qkv.weight", h16), N)
-                call("sed_mhsa_fwd", q, k, v, o16, lse, Bx, H, N, Npad, f16)
-                x_mid = x_in
-                gemm_nt(o16, W[p + "attn.proj.weight"].w, EPI_F32_RESID, bias=self.P(p + "attn.proj.bias"), res=x_in, outF=x_mid,
-                        gbias=gb("attn.proj.weight", o16), gb_rows=N)
-                call("sed_layernorm_fwd", x_mid, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-6, 1.0, h2, None,
-                     mean2, rstd2, M, D, f16)
-                gemm_nt(h2, W[p + "mlp.fc1.weight"].w, EPI_GELU, bias=self.P(p + "mlp.fc1.bias"), outH=None, outH2=act,
-                        gbias=gb("mlp.fc1.weight", h2), gb_rows=N)
-                x_out = x_mid
-                gemm_nt(act, W[p + "mlp.fc2.weight"].w, EPI_F32_RESID, bias=self.P(p + "mlp.fc2.bias"), res=x_mid, outF=x_out,
-                        gbias=gb("mlp.fc2.weight", act), gb_rows=N)
-                x = x_out
-                if li + 1 == m.passt_feature_layer:
-                    pooled = self._fpool_fwd(W, x, Bx, tp, save, ctx)
-                    if not want_frame:
-                        break
-                continue
-            call("sed_gemm_qkv", h16, W[p + "attn.qkv.weight"].w, self.P(p + "attn.qkv.bias"), M, D, H, N, Npad, q, k,
-                 v, None, None, None, None, None, None, None, f16)
-            call("sed_mhsa_fwd", q, k, v, o16, lse, Bx, H, N, Npad, f16)
-            x_mid = E(Bx, N, D) if sv else x_in
-            gemm_nt(o16, W[p + "attn.proj.weight"].w, EPI_F32_RESID, bias=self.P(p + "attn.proj.bias"), res=x_in,
-                    outF=x_mid)
-            if dual:
-                call("sed_layernorm_fwd_dual", x_mid, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-6, 1.0, h2, h2s, mean2, rstd2, M, D)
+                f32_out = last or li + 1 == m.passt_feature_layer
+                call(lnp, act, W[p + "mlp.fc2.weight"].w, M, D, 4 * D, 64 if slab_act else 4 * D, 4 * D, self.P(p + "mlp.fc2.bias"),
+                     None, x16f, xlo, x_in if f32_out else None, x16f, None if f32_out else xlo, partf, D)
+                planes = not f32_out
+                if not last:
+                    call("sed_ln_fold_stats", partf, statf, M, D // 64, D, 1e-6)
+                    have_stat = True
+                x_out = x_in
             else:
-                call("sed_layernorm_fwd", x_mid, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-6, 1.0, h2, None,
-                     mean2, rstd2, M, D, f16)
-            gemm_nt(h2, W[p + "mlp.fc1.weight"].w, EPI_GELU, bias=self.P(p + "mlp.fc1.bias"), outH=hpre if sv else None,
-                    outH2=act)
-            x_out = E(Bx, N, D) if sv else x_mid
-            gemm_nt(act, W[p + "mlp.fc2.weight"].w, EPI_F32_RESID, bias=self.P(p + "mlp.fc2.bias"), res=x_mid,
-                    outF=x_out)
+                if f_qkv == "w2f8":
+                    img, s = self._w2f8_image(W, wq)
+                    call("sed_gemm_qkv_w2f8", h16, img, bq, M, D, H, N, Npad, q, k, v, s)
+                elif f_qkv == "w2":
+                    call("sed_gemm_qkv_w2", h16, self._w2_image(W, wq), bq, M, D, H, N, Npad, q, k, v, f16)
+                elif f_qkv == "gb":
+                    call("sed_gemm_qkv_gb", h16, W[wq].w, bq, M, D, H, N, Npad, q, k, v, f16, self._wcorr_bias(W, wq, h16, Bx, N), N)
+                else:
+                    call("sed_gemm_qkv", h16, W[wq].w, bq, M, D, H, N, Npad, q, k, v, None, None, None, None, None, None, None, f16)
+                call("sed_mhsa_fwd", q, k, v, o16, lse, Bx, H, N, Npad, f16 | (4 if p8 else 0))
+                x_mid = E(Bx, N, D) if sv else x_in
+                linear(p, "attn.proj", f_proj, o16, EPI_F32_RESID, D, res=x_in, outF=x_mid)
+                if dual:
+                    call("sed_layernorm_fwd_dual", x_mid, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-6, 1.0, h2, h2s, mean2, rstd2, M, D)
+                else:
+                    call("sed_layernorm_fwd", x_mid, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-6, 1.0, h2, None,
+                         mean2, rstd2, M, D, f16)
+                if f28:     # fc1's gb form whose epilogue also writes the e4m3 image of the activation beside it, for fc2's lo product
+                    call("sed_gemm_nt_gb_e4m3", h2, W[p + "mlp.fc1.weight"].w, M, 4 * D, D, D, D, self.P(p + "mlp.fc1.bias"), act, 4 * pitch(f28),
+                         self._wcorr_bias(W, p + "mlp.fc1.weight", h2, Bx, N), N)
+                else:
+                    linear(p, "mlp.fc1", f_fc1, h2, EPI_GELU, D, outH=hpre, outH2=act)
+                x_out = E(Bx, N, D) if sv else x_mid
+                linear(p, "mlp.fc2", f_fc2, act, EPI_F32_RESID, 4 * D, res=x_mid, outF=x_out)
             if sv:
-                L.update(x_in=x_in, h16=h16s if dual else h16, q=q, k=k, v=v, o16=o16, lse=lse, x_mid=x_mid, h2=h2s if dual else h2,
-                         hpre=hpre, act=act, mean1=mean1, rstd1=rstd1, mean2=mean2, rstd2=rstd2)
-                ctx["layers"].append(L)
+                ctx["layers"].append(dict(x_in=x_in, h16=h16s if dual else h16, q=q, k=k, v=v, o16=o16, lse=lse, x_mid=x_mid,
+                                          h2=h2s if dual else h2, hpre=hpre, act=act, mean1=mean1, rstd1=rstd1, mean2=mean2, rstd2=rstd2))
             elif save:
                 ctx["layers"].append(None)      # (a frozen block below the lowest trainable one: index kept, nothing saved)
             x = x_out
@@ -607,8 +506,8 @@ class SedEngine:
                 pooled = self._fpool_fwd(W, x, Bx, tp, save, ctx)
                 if not want_frame:
                     break  # later blocks only feed the AT head (`frame`); windows never need them
-                if save and not (li + 1 >= lo_f):
-                    x = x.clone()           # the in-place blocks that follow must not touch the tensor f_pool's backward reads
+                if save and (fold or li + 1 < lo_f):
+                    x = x.clone()       # f_pool's backward reads the tensor it was given; the in-place blocks that follow must not touch it
         frame16 = None
         if want_frame:
             frame16 = E(M, D, dt=A16)
@@ -1305,8 +1204,8 @@ class SedEngine:
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         g2 = g.view(M, D)
         # The LayerNorm backward kernels leave the bf16 image of the residual-stream gradient they just updated: it is the dY operand of the
-        # next weight-gradient / dX GEMMs (no cast pass over the fp32 stream; the bias gradient comes out of the TN kernel).  SED_LN_BWD16=0 off.
-        x16_on = self.ln_bwd16 and self.dw_tn
+        # next weight-gradient / dX GEMMs (no cast pass over the fp32 stream; the bias gradient comes out of the TN kernel).
+        x16_on = self.dw_tn
         gin16 = self._g16_take(g)
         # ---- MLP branch: x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))
         dln = self._mlp_bwd(W, p + "mlp.fc1", p + "mlp.fc2", g2, L["h2"], L["hpre"], L["act"], M, G, residual=None, dy16=gin16)
@@ -1369,8 +1268,8 @@ class SedEngine:
         dOh = E(B * H, T, 64, dt=BF16)
         dOt = E(B * H, 64, Tpad, dt=BF16)
         dSt = self._zeros(("dSt", B, Tpad), (B * H, Tpad, Tpad), BF16, dev)      # scratch of this call: one buffer for all layers
-        # P^T slab beside it: dK / dV as contractions over the two stored slabs (SED_RELPOS_DKDV=recompute: the score-recomputing kernel)
-        Pst = self._zeros(("Pst", B, Tpad), (B * H, Tpad, Tpad), BF16, dev) if self.relpos_stream else None
+        # P^T slab beside it: dK / dV as contractions over the two stored slabs the dQ kernel writes, instead of recomputing the scores
+        Pst = self._zeros(("Pst", B, Tpad), (B * H, Tpad, Tpad), BF16, dev)
         dP = torch.zeros(Rpad, Da, dtype=F32, device=dev)
         # (local window: the pooled slabs may hold the full-window content of an earlier call outside the band -- the band kernels
         #  neither write nor read those tiles, see relpos_attention.hip band_tile_lo / band_tile_hi)

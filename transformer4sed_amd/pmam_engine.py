@@ -50,7 +50,7 @@ class PmamEngine(SedEngine):
         self.small_dw = True
         self.cg_fused16 = True
         if not self.split:
-            raise RuntimeError("the PMAM path runs its 384-wide context network in split precision (SED_DECODER_SPLIT=1, f16 forward)")
+            raise RuntimeError("the PMAM path runs its 384-wide context network in split precision (engine.split, f16 forward)")
         self.dec_terms2 = False      # (its own context-network schedule below keeps three terms in every GEMM)
         self._drop_gen = None
 
