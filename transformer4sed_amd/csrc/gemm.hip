@@ -736,7 +736,7 @@ struct V3Side {
     uint2 a[EPI == EPI_DGELU ? 8 : 1];
 };
 // SM (side mode of the LayerNorm-fold producer): 0 = not a producer, 1 = fp32 residual, 2 = f16 hi + f16 lo planes, 3 = f16 hi + byte lo.
-// A compile-time mode (pp_epilogue dispatches on the launch's pointers): with the three load forms as run-time branches of one function
+// A compile-time mode (part of the kernel variant, PpTraits::side_mode): with the three load forms as run-time branches of one function
 // their results meet in register copies right behind the loads, and every batch waits for its own round trip.
 template <int EPI, int SM = 0>
 __device__ __forceinline__ void v3_side_load(V3Side<EPI>& sd, const GemmArgs& g, int m0, int n, int lane) {
@@ -1178,13 +1178,50 @@ __device__ __forceinline__ void v3_load_consts(V3Consts<EPI>& c, const GemmArgs&
     }
 }
 
-template <int EPI, bool F16, int GBM, int RB = 8, bool F8 = false>
+// ---------------------------------------------------------------------------------------------------------------------
+// Variants of the 256^2 kernel: the third template argument of gemm_nt_pp_kernel / pp_epilogue (an int: the kernels' symbol names carry
+// the number).  pp_select<EPI> (host) is the only place that picks one, PpTraits the only place that says what one means.  All but
+// PP_PLAIN and PP_QKV_ROWS take f16 operands only and exist for the encoder epilogues EPI_F32_RESID / EPI_GELU / EPI_QKV; the folded-
+// LayerNorm producer is EPI_F32_RESID, its consumers EPI_GELU / EPI_QKV (GemmArgs.rowpart ..).  RB = 7: 224-row tiles; F8: fp8 K tiles.
+//   PP_PLAIN              every EPI but EPI_ATOMIC, RB 7 / 8.  A [M, K], B [N, K]; EPI_F32 / EPI_F32_RESID / EPI_DGELU store straight from
+//                         the accumulators, EPI_QKV writes every requested output (row-major, transposed, biased second q)
+//   PP_GROUP_BIAS         + gbias[m / gb_rows][n].  With F8 (EPI_GELU only): outH2 rows carry their e4m3 image; no fp8 K tile is walked
+//   PP_TWO_TERM           B = [hi | lo] ([hi | hi | lo] with b_skip), the A panel walked twice (k_wrap).  With F8 (EPI_F32_RESID / EPI_GELU):
+//                         A and B rows [f16 | e4m3], K / 64 f16 tiles then k8 fp8 tiles, no wrap
+//   PP_LN                 RB 7 / 8.  Producer: fp32 residual in; fp32 stream + f16 image + rowpart out.  Consumer: rstd (acc - mean colS) + bias
+//                         from rowstat / colS; EPI_QKV: q / k / v row-major only
+//   PP_QKV_ROWS           EPI_QKV, RB 7 / 8.  PP_PLAIN's operands; q / k / v row-major only (no transposed copies, second q or pos_u), stored
+//                         straight from the accumulators
+//   PP_LN_PLANES16        producer, RB 7 / 8: residual in as f16 hi + f16 lo planes; fp32 + f16 image or the planes out
+//   PP_LN_PLANES8         producer, RB 7 / 8: f16 hi (slab-major) + byte lo planes in and out, stored straight from the accumulators
+//   PP_LN_PLANES8_F32OUT  producer, RB 7 / 8: f16 hi + byte lo planes in; fp32 stream + f16 image out
+//   PP_TWO_TERM_QKV_ROWS  EPI_QKV: PP_TWO_TERM's operands and K walk (f16 or F8) with PP_QKV_ROWS' epilogue
+// ---------------------------------------------------------------------------------------------------------------------
+enum { PP_PLAIN = 0, PP_GROUP_BIAS = 1, PP_TWO_TERM = 2, PP_LN = 3, PP_QKV_ROWS = 4, PP_LN_PLANES16 = 5, PP_LN_PLANES8 = 6,
+       PP_LN_PLANES8_F32OUT = 7, PP_TWO_TERM_QKV_ROWS = 8 };
+template <int V, bool F8 = false>
+struct PpTraits {
+    static constexpr bool plain = V == PP_PLAIN;
+    static constexpr bool group_bias = V == PP_GROUP_BIAS;
+    static constexpr bool two_term = V == PP_TWO_TERM || V == PP_TWO_TERM_QKV_ROWS;
+    static constexpr bool two_term_walk = two_term && !F8;      // the A panel wraps at k_wrap (the F8 forms walk their [f16 | e4m3] rows once)
+    static constexpr bool ln = V == PP_LN || V == PP_LN_PLANES16 || V == PP_LN_PLANES8 || V == PP_LN_PLANES8_F32OUT;
+    static constexpr bool planes8_out = V == PP_LN_PLANES8;
+    static constexpr bool rows_only = ln || V == PP_QKV_ROWS || V == PP_TWO_TERM_QKV_ROWS;      // head split: row-major q / k / v only
+    static constexpr bool slab_a = !group_bias && !two_term;      // (the evaluation-mode variants have no register to spare for slab-major A)
+    // SM of v3_side_load / v3_store_batch, the producer's residual form: 0 = not a producer, 1 = fp32, 2 = f16 + f16 planes, 3 = f16 + byte planes
+    static constexpr int side_mode(int epi) { return !(ln && epi == EPI_F32_RESID) ? 0 : (V == PP_LN ? 1 : (V == PP_LN_PLANES16 ? 2 : 3)); }
+    // epilogues that store straight from the accumulators and leave the LDS alone
+    static constexpr bool direct_epi(int epi) { return epi == EPI_BF16 || epi == EPI_GELU || (epi == EPI_QKV && rows_only); }
+    // fp32 straight from the accumulators (B rows in PP_COL32 column order)
+    static constexpr bool f32_direct(int epi) { return plain && (epi == EPI_F32 || epi == EPI_F32_RESID); }
+};
+
+template <int EPI, bool F16, int V, int RB = 8, bool F8 = false>
 __device__ __forceinline__ void pp_epilogue(const GemmArgs& g, const f32x4_t (&acc)[8][4], const V3Consts<EPI>& cc,
                                             unsigned char* wl, int mb, int nb, int lane, unsigned long long* gxt = nullptr) {
     // mb = first row of this wave's 128 x 64 sub-tile, nb = its first column
-    constexpr bool GB = GBM == 1;   // 1: row-group bias, 2: two-term weights (plain epilogue), 3: folded LayerNorm (producer / consumer by EPI)
-    constexpr bool LN = GBM == 3 || (GBM >= 5 && GBM <= 7);      // (5: producer reading f16 + f16 planes; 6 / 7: f16 + byte planes, writing planes / fp32)
-    constexpr bool ROWS_ONLY = GBM >= 3;      // head-split epilogue: row-major q / k / v only (3: folded LayerNorm, 4: the plain encoder form)
+    using T = PpTraits<V, F8>;
     const int l15 = lane & 15, lq = lane >> 4;
     if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU) {
         // 16-byte stores straight from the accumulators (PP_COL column order): no staging, no wave barrier
@@ -1203,12 +1240,12 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& g, const f32x4_t (&a
             const PPSinkRowsT<F8> sink{ob + (size_t)(mb + r8) * ldo + 32 * hk + 8 * lq, ob + (size_t)(mb + lrow) * ldo + 8 * lq,
                                        8 * ldo, g.M - mb - r8, g.M - mb - lrow, lrow < 8,
                                        (F8 && g.out_e4m3) ? 2 * g.N - (nb + 32 * hk + 8 * lq) : 0};
-            if constexpr (GB) {      // evaluation-mode encoder only (no saved pre-activation: one pass)
+            if constexpr (T::group_bias) {      // evaluation-mode encoder only (no saved pre-activation: one pass)
                 const float *rA, *rB;
                 const int bnd = gb_split(g, mb, rA, rB);
                 if (EPI == EPI_GELU && pass == 1) pp_stage16_gb<F16, 1>(sink, acc, cc.bv, rA + nb, rB + nb, bnd, l15, lq);
                 else pp_stage16_gb<F16, 0>(sink, acc, cc.bv, rA + nb, rB + nb, bnd, l15, lq);
-            } else if constexpr (LN) {      // consumer: Linear(LayerNorm(x)) from the raw stream's product (no saved pre-activation either)
+            } else if constexpr (T::ln) {      // consumer: Linear(LayerNorm(x)) from the raw stream's product (no saved pre-activation either)
                 if (EPI == EPI_GELU && pass == 1) pp_stage16_ln<F16, 1, false, RB>(sink, acc, cc.bv, g.colS + nb, g.rowstat, mb, g.M, l15, lq);
                 else pp_stage16_ln<F16, 0, false, RB>(sink, acc, cc.bv, g.colS + nb, g.rowstat, mb, g.M, l15, lq);
             } else
@@ -1225,7 +1262,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& g, const f32x4_t (&a
         const int D = g.heads * 64;
         const int which = nb / D, h = (nb - which * D) >> 6;
         bf16_t* row_dst = which == 0 ? g.q : (which == 1 ? g.k : g.v);
-        if constexpr (ROWS_ONLY) {
+        if constexpr (T::rows_only) {
             // (folded-LayerNorm consumer / plain encoder form: row-major q / k / v only -- no second biased q, no transposed copies.)
             // Stored straight from the accumulators: a lane's 8 columns of a half are 16 contiguous bytes of one head row.
             if (row_dst == nullptr) return;      // (the row-major V is only needed by the backward: inference passes v = NULL)
@@ -1234,7 +1271,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& g, const f32x4_t (&a
             const int m_first = mb + (lrow & 7), b0 = m_first / g.seq;
             const PPSinkHeads sink{row_dst + (size_t)h * g.seq * 64 + 32 * (lrow >> 3) + 8 * lq, b0, m_first - b0 * g.seq, g.seq, g.heads * g.seq,
                                    g.M - m_first, lrow < 8};
-            if constexpr (LN) {
+            if constexpr (T::ln) {
                 float bv[4][4];
                 pp_stage16_ln<F16, 0, true, RB>(sink, acc, bv, g.colS + nb, g.rowstat, mb, g.M, l15, lq, g.bias + nb);
             } else {
@@ -1254,7 +1291,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& g, const f32x4_t (&a
             bf16_t* td = pass == 0 ? tr_dst : g.q2t;
             float bv[4][4];
             pp_col_consts(bv, g.bias != nullptr ? g.bias + nb : nullptr, extra, lq);
-            if constexpr (GB) {
+            if constexpr (T::group_bias) {
                 const float *rA, *rB;
                 const int bnd = gb_split(g, mb, rA, rB);
                 pp_stage16_gb_k<F16, 0>(lsink, acc, bv, rA + nb, rB + nb, bnd, l15, lq);
@@ -1326,15 +1363,15 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& g, const f32x4_t (&a
         }
         return;
     }
-    if constexpr ((EPI == EPI_F32 || EPI == EPI_F32_RESID) && GBM == 0) {
+    if constexpr (T::f32_direct(EPI)) {
         pp_epilogue_f32_direct<EPI, RB>(g, acc, mb, nb, lane);
         return;
     }
-    if constexpr (EPI == EPI_DGELU && GBM == 0) {
+    if constexpr (EPI == EPI_DGELU && T::plain) {
         pp_epilogue_dgelu_direct<F16, RB>(g, acc, mb, nb, lane);
         return;
     }
-    if constexpr (EPI == EPI_F32_RESID && GBM == 6) {      // byte planes in -> byte planes out: straight from the accumulators
+    if constexpr (EPI == EPI_F32_RESID && T::planes8_out) {      // byte planes in -> byte planes out: straight from the accumulators
         pp_epilogue_lo8_direct<RB>(g, const_cast<f32x4_t (&)[8][4]>(acc), mb, nb, lane);
         return;
     }
@@ -1346,7 +1383,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& g, const f32x4_t (&a
     float4 b = make_float4(cc.bv[0][0], cc.bv[0][1], cc.bv[0][2], cc.bv[0][3]);
     float4 bB = b;
     int mbnd = 0x7fffffff;
-    if constexpr (GB) {
+    if constexpr (T::group_bias) {
         const float *rA, *rB;
         mbnd = mb + gb_split(g, mb, rA, rB);
         const float4 xa = *reinterpret_cast<const float4*>(rA + n), xb = *reinterpret_cast<const float4*>(rB + n);
@@ -1354,8 +1391,7 @@ __device__ __forceinline__ void pp_epilogue(const GemmArgs& g, const f32x4_t (&a
         b = make_float4(b.x + xa.x, b.y + xa.y, b.z + xa.z, b.w + xa.w);
     }
     const int mend = mb + 16 * RB;
-    // (the producer's residual form is part of the kernel variant: GBM 3 = fp32, 5 = f16 + f16 planes, 6 = f16 + byte planes -- see v3_side_load)
-    constexpr int SM = (LN && EPI == EPI_F32_RESID) ? (GBM >= 6 ? 3 : (GBM == 5 ? 2 : 1)) : 0;
+    constexpr int SM = T::side_mode(EPI);      // (the producer's residual form is part of the kernel variant -- see v3_side_load)
 #ifdef ABL_NO_EPI
     if constexpr (SM >= 2) return;
 #endif
@@ -1386,7 +1422,7 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // RB = 16-row blocks per wave row: 8 -> 256-row tiles; 7 -> 224-row tiles (the eighth block's reads, MFMAs and stores are skipped; its
 // LDS rows are still filled so that every wave keeps the same DMA count for the counted waits).  With M = 38080 tokens on 256 CUs the
 // N = 768 / 2304 GEMMs are 447 / 1341 tiles of 256 rows = 1.75 / 5.24 rounds, i.e. 2 / 6 rounds with 13 % of the last ones empty; as
-// 510 / 1530 tiles of 224 rows they are 1.99 / 5.98 rounds of tiles that are 12.5 % shorter -- launch_gemm picks the cheaper height.
+// 510 / 1530 tiles of 224 rows they are 1.99 / 5.98 rounds of tiles that are 12.5 % shorter -- pp_geometry picks the cheaper height.
 typedef int i32x8_t __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ i32x8_t cat32(s16x8_t a, s16x8_t b) {
     typedef int i32x4_t __attribute__((ext_vector_type(4)));
@@ -1403,8 +1439,9 @@ __device__ __forceinline__ void mfma16_f16_tied(f32x4_t& c, s16x8_t a, s16x8_t b
 __device__ __forceinline__ void mfma128_e4m3_tied(f32x4_t& c, i32x8_t a, i32x8_t b, int sc) {
     asm volatile("v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %3 op_sel_hi:[0,0,0]" : "+v"(c) : "v"(a), "v"(b), "v"(sc));
 }
-template <int EPI, bool F16, int GB = 0, int RB = 8, bool F8 = false>
+template <int EPI, bool F16, int V = PP_PLAIN, int RB = 8, bool F8 = false>
 __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmArgs g) {
+    using T = PpTraits<V, F8>;
     constexpr int TM = 32 * RB;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds3[];
 #ifdef GX_TRACE
@@ -1439,8 +1476,8 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmArgs g) {
     }
     // Epilogues that store straight from the accumulators leave the LDS alone: the next tile's first operand stage is requested BEFORE
     // the epilogue (its DMA lands under the stores) and the end-of-tile workgroup barrier goes away.
-    constexpr bool DIRECT_EPI = (EPI == EPI_BF16 || EPI == EPI_GELU || (EPI == EPI_QKV && GB >= 3));
-    constexpr bool F32L = (EPI == EPI_F32 || EPI == EPI_F32_RESID) && GB == 0;      // fp32 straight from the accumulators: PP_COL32 column order
+    constexpr bool DIRECT_EPI = T::direct_epi(EPI);
+    constexpr bool F32L = T::f32_direct(EPI);      // PP_COL32 column order
     auto tile_mn = [&](int tl_, int& m0_, int& n0_) {
         const int t = xcd_remap(tl_, nwg);
         const int GM = g.group_m;
@@ -1460,7 +1497,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmArgs g) {
     const int rows_a = (g.M - m0) < TM ? (g.M - m0) : TM;
     // (slab-major A, GemmArgs.a_slab: row pitch 128 bytes, K tile kt at kt * M * 128; rows past M read the next slab -- they only reach
     //  accumulator rows that are never stored -- and nothing is read past the last slab's end)
-    const bool a_slab = (GB == 1 || GB == 2 || GB == 8) ? false : g.a_slab != 0;      // (the evaluation-mode variants have no register to spare for it)
+    const bool a_slab = T::slab_a ? g.a_slab != 0 : false;
     const int a_ld2 = a_slab ? 128 : g.lda * 2, a_kst = a_slab ? g.M * 128 : BK * 2;
     const __amdgpu_buffer_rsrc_t ra = a_slab
         ? __builtin_amdgcn_make_buffer_rsrc((void*)(g.A + (size_t)m0 * 64), 0, (unsigned)((size_t)(g.K / BK) * g.M * 128 - (size_t)m0 * 128), 0x00020000)
@@ -1494,7 +1531,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmArgs g) {
     }
 #define PP_DMA_R(RA_, RB_, SL, KT)                                                                                        \
     {                                                                                                                     \
-        const int kt_ = ((GB == 2 || GB == 8) && !F8 && (KT) >= g.k_wrap) ? (((SL) == 0 || (SL) == 3) ? (KT) - g.k_wrap : (KT) + g.b_skip) : (KT); \
+        const int kt_ = (T::two_term_walk && (KT) >= g.k_wrap) ? (((SL) == 0 || (SL) == 3) ? (KT) - g.k_wrap : (KT) + g.b_skip) : (KT);              \
         const int so_ = kt_ * (((SL) == 1 || (SL) == 2) ? BK * 2 : a_kst), st_ = ((KT) & 1) << 15;                        \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(((SL) == 1 || (SL) == 2) ? RB_ : RA_, (lds_ptr_t)(lds3 + st_ + ld_[SL][0]), 16, vo[SL][0], so_, 0, 0); \
         __builtin_amdgcn_raw_ptr_buffer_load_lds(((SL) == 1 || (SL) == 2) ? RB_ : RA_, (lds_ptr_t)(lds3 + st_ + ld_[SL][1]), 16, vo[SL][1], so_, 0, 0); \
@@ -1639,7 +1676,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmArgs g) {
 #undef PP_TILE8
 #undef PP_TILE_
 #ifdef GX_TRACE
-    pp_epilogue<EPI, F16, GB, RB, F8>(g, acc, cc, lds3 + wave * V3_WLDS, m0 + wm * (16 * RB), n0 + wn * 64, lane, gx_t);
+    pp_epilogue<EPI, F16, V, RB, F8>(g, acc, cc, lds3 + wave * V3_WLDS, m0 + wm * (16 * RB), n0 + wn * 64, lane, gx_t);
     GX_STAMP(5)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     GX_STAMP(6)
@@ -1662,7 +1699,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmArgs g) {
         }
     }
 #else
-    pp_epilogue<EPI, F16, GB, RB, F8>(g, acc, cc, lds3 + wave * V3_WLDS, m0 + wm * (16 * RB), n0 + wn * 64, lane);
+    pp_epilogue<EPI, F16, V, RB, F8>(g, acc, cc, lds3 + wave * V3_WLDS, m0 + wm * (16 * RB), n0 + wn * 64, lane);
 #endif
     if constexpr (DIRECT_EPI) {
         tl = tl_next;                        // (no barrier: nothing of this tile is left in the LDS)
@@ -2088,6 +2125,110 @@ extern "C" int sed_gemm_dw_tn(const void* dY, const void* X, int x_f16, int T, i
     return sed_check_launch();
 }
 
+// ---- host side of the 256^2 kernel: geometry (pp_geometry), kernel selection (pp_select<EPI>), launch (pp_launch<...>) ----
+// Fills the launch-geometry fields of g (group_m, persist, tile_ctr) and returns the grid; use7 = 224-row tiles.
+static unsigned pp_geometry(GemmArgs& g, bool& use7) {
+    // L2 grouping: 4 tile rows x all tile columns per group, groups XCD-contiguous.  Swept 2..32 on the model's shapes
+    // (tools/gemm_l2.py): fabric reads stay at 1.4-2.3x (N = 768) / ~5x (N = 3072) of the algorithmic operand bytes for every
+    // height -- column tiles of one row panel drift apart by more than the ~2 K-steps a line survives in the 4 MB L2 and re-read it
+    // from the Infinity Cache -- while the time is best at 4 (fc2 1186 vs 998 TFLOP/s at 2): the counter does not track the time.
+    g.group_m = 4;
+    // SED_GEMM_RB (read per launch): 7 / 8 force a tile height (A/B and the bit-exactness test), 0 = choose by the round count below.
+    // Default 8: alone on the GPU the 224-row form wins 3-4 % on the N = 768 shapes, but inside the train step the teacher's and the
+    // weight-gradient streams fill the last round's idle CUs anyway and the shorter tiles cost 0.25 % (104.03 vs 103.77 ms, 3 A/B pairs).
+    const char* rb_s = getenv("SED_GEMM_RB");
+    const int rb_env = rb_s ? atoi(rb_s) : 8;
+    static int ncu_dev = 0;
+    if (ncu_dev == 0) {
+        int dev = 0, n = 0;
+        (void)hipGetDevice(&dev);
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        ncu_dev = n;
+    }
+    const int ncu = cu_budget(ncu_dev) & ~7;   // whole XCD rounds: blockIdx.x & 7 must stay the XCD of every tile a workgroup walks
+    // Tile height: rounds of workgroups x rows per tile is what the launch costs; 224-row tiles win when they fill the last round
+    // that 256-row tiles leave mostly empty (M = 38080: 2 x 256 vs 2 x 224 for N = 768, 6 x 256 vs 6 x 224 for N = 2304).
+    // (the row-group-bias and two-term variants exist with 256-row tiles only)
+    const int ntn = g.N / V3_T;
+    const long long t8 = (long long)cdiv(g.M, 256) * ntn, t7 = (long long)cdiv(g.M, 224) * ntn;
+    const long long c8 = ((t8 + ncu - 1) / ncu) * 256, c7 = ((t7 + ncu - 1) / ncu) * 224;
+    use7 = g.gbias == nullptr && g.k_wrap == 0 && g.k8 == 0 && (rb_env == 7 || (rb_env == 0 && c7 * 100 < c8 * 97));
+    // Persistent form whenever there are more tiles than CUs (one workgroup per tile lost its A/B in round 3 and has no switch any more)
+    const unsigned tiles = (unsigned)(use7 ? t7 : t8);
+    g.persist = (int)tiles > ncu ? 1 : 0;
+    // SED_GEMM_DYN (read per launch; default 1): dynamic tile walk of the persistent form, 0 = the static walk (bit-identical results)
+    const char* dy = getenv("SED_GEMM_DYN");
+    g.tile_ctr = (g.persist && !(dy && atoi(dy) == 0)) ? dyn_counter_slot() : nullptr;
+    return g.persist ? (unsigned)ncu : tiles;
+}
+
+// Launch of one instantiation; its dynamic-LDS limit is raised once per process (each process owns one device).
+typedef void (*PpLaunch)(const GemmArgs&, unsigned, hipStream_t);
+template <int EPI, bool F16, int V, int RB = 8, bool F8 = false>
+static void pp_launch(const GemmArgs& g, unsigned grid, hipStream_t s) {
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, F16, V, RB, F8>, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS); attr = true; }
+    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, F16, V, RB, F8>), dim3(grid, 1), dim3(512), V3_LDS, s, g);
+}
+template <int EPI, bool F16, int V>
+static PpLaunch pp_tile_height(bool use7) { return use7 ? &pp_launch<EPI, F16, V, 7> : &pp_launch<EPI, F16, V, 8>; }
+template <int EPI, int V>
+static PpLaunch pp_type_and_height(int f16, bool use7) { return f16 ? pp_tile_height<EPI, true, V>(use7) : pp_tile_height<EPI, false, V>(use7); }
+
+// The kernel a 256^2 launch goes to, or nullptr for an argument set no variant serves.  A pure function of its arguments; the variant
+// table is beside PP_PLAIN.  (use7 is false whenever gbias, k_wrap or k8 is set: pp_geometry.)
+template <int EPI>
+static PpLaunch pp_select(const GemmArgs& g, int f16, bool use7) {
+    constexpr bool ENC = EPI == EPI_F32_RESID || EPI == EPI_GELU || EPI == EPI_QKV;      // the epilogues the special variants exist for
+    if ((long long)g.lda * 2 * V3_T >= (1LL << 31) || (long long)g.ldb * 2 * V3_T >= (1LL << 31)) return nullptr;  // 32-bit panel offsets
+    // head split with row-major q / k / v only: no transposed copies, no biased second q, no pos_u
+    const bool rows_only = g.qt == nullptr && g.kt == nullptr && g.vt == nullptr && g.q2 == nullptr && g.q2t == nullptr && g.pu == nullptr;
+    const int nk = g.K / BK;
+    if (g.rowpart != nullptr || g.rowstat != nullptr) {
+        // folded LayerNorm: producer (residual epilogue) or consumer (head-split / fused-GELU epilogue); f16, no other special mode
+        if constexpr (ENC) {
+            if (!f16 || g.gbias != nullptr || g.k_wrap != 0 || (g.N & 63)) return nullptr;
+            if constexpr (EPI == EPI_F32_RESID) {
+                if (g.rowpart == nullptr || g.outH == nullptr || g.rowstat != nullptr) return nullptr;
+                if (g.res_lo != nullptr && g.lo8) return g.out_lo != nullptr ? pp_tile_height<EPI, true, PP_LN_PLANES8>(use7) : pp_tile_height<EPI, true, PP_LN_PLANES8_F32OUT>(use7);
+                if (g.res_lo != nullptr) return pp_tile_height<EPI, true, PP_LN_PLANES16>(use7);
+            } else {
+                if (g.rowstat == nullptr || g.colS == nullptr || g.rowpart != nullptr) return nullptr;
+            }
+            return pp_tile_height<EPI, true, PP_LN>(use7);
+        }
+        return nullptr;
+    }
+    if (g.k8 != 0) {
+        // two-term weights, lo product on the fp8 matrix path: the two-term variants' epilogues behind a K walk of f16 tiles followed by
+        // e4m3 tiles (an even number of f16 tiles, at least one)
+        if constexpr (ENC) {
+            if (!f16 || g.gbias != nullptr || g.k_wrap != 0 || g.a_slab || ((nk - g.k8) & 1) || g.k8 >= nk) return nullptr;
+            if constexpr (EPI == EPI_QKV) return rows_only ? &pp_launch<EPI, true, PP_TWO_TERM_QKV_ROWS, 8, true> : nullptr;
+            else return &pp_launch<EPI, true, PP_TWO_TERM, 8, true>;
+        }
+        return nullptr;
+    }
+    if (g.gbias != nullptr || g.k_wrap != 0) {
+        // row-group bias / two-term weights: evaluation-mode encoder GEMMs only (f16 operands)
+        if constexpr (ENC) {
+            if (!f16 || (g.gbias != nullptr && g.k_wrap != 0)) return nullptr;
+            if constexpr (EPI == EPI_QKV) if (g.k_wrap != 0 && rows_only) return &pp_launch<EPI, true, PP_TWO_TERM_QKV_ROWS>;
+            if constexpr (EPI == EPI_GELU) if (g.out_e4m3) {
+                // row-group bias + the e4m3 image of the output (fc1 of the evaluation-mode encoder in its fp8 form: f16 weights + mean
+                // correction, the activation leaves as fc2's two-image A operand): the F8 kernel with no fp8 K tiles
+                return (g.k_wrap != 0 || (nk & 1)) ? nullptr : &pp_launch<EPI, true, PP_GROUP_BIAS, 8, true>;
+            }
+            return g.k_wrap != 0 ? &pp_launch<EPI, true, PP_TWO_TERM> : &pp_launch<EPI, true, PP_GROUP_BIAS>;
+        }
+        return nullptr;
+    }
+    // the encoder's form of the head split (its attention kernels transpose in LDS): a kernel without the other outputs' paths, 3 % faster
+    // than carrying them as run-time branches
+    if constexpr (EPI == EPI_QKV) if (rows_only) return pp_type_and_height<EPI, PP_QKV_ROWS>(f16, use7);
+    return pp_type_and_height<EPI, PP_PLAIN>(f16, use7);
+}
+
 template <int EPI>
 static int launch_gemm(const GemmArgs& g, int f16, hipStream_t s) {
     if (g.M <= 0 || g.N % TILE != 0 || g.K % BK != 0 || g.ksplit < 1) return SED_ERR_ARG;
@@ -2095,157 +2236,12 @@ static int launch_gemm(const GemmArgs& g, int f16, hipStream_t s) {
     // 256^2 kernel: every forward / dX GEMM of the model (N % 256 == 0, M >= 1024).  The split-K weight-gradient GEMMs of the NT
     // form stay on the 128^2 kernel (two workgroups per CU cover its atomic epilogue).
     if constexpr (EPI != EPI_ATOMIC) if (g.N % V3_T == 0 && g.M >= 1024 && g.ksplit == 1) {
-        if ((long long)g.lda * 2 * V3_T >= (1LL << 31) || (long long)g.ldb * 2 * V3_T >= (1LL << 31)) return SED_ERR_ARG;  // 32-bit panel offsets
-        // L2 grouping: 4 tile rows x all tile columns per group, groups XCD-contiguous.  Swept 2..32 on the model's shapes
-        // (tools/gemm_l2.py): fabric reads stay at 1.4-2.3x (N = 768) / ~5x (N = 3072) of the algorithmic operand bytes for every
-        // height -- column tiles of one row panel drift apart by more than the ~2 K-steps a line survives in the 4 MB L2 and re-read it
-        // from the Infinity Cache -- while the time is best at 4 (fc2 1186 vs 998 TFLOP/s at 2): the counter does not track the time.
         GemmArgs gg = g;
-        gg.group_m = 4;
-        const int persist_env = 1;      // (round 6: SED_GEMM_PERSIST=0, one workgroup per tile, lost its A/B in round 3 and is gone)
-        // SED_GEMM_RB (read per launch): 7 / 8 force a tile height (A/B and the bit-exactness test), 0 = choose by the round count below.
-        // Default 8: alone on the GPU the 224-row form wins 3-4 % on the N = 768 shapes, but inside the train step the teacher's and the
-        // weight-gradient streams fill the last round's idle CUs anyway and the shorter tiles cost 0.25 % (104.03 vs 103.77 ms, 3 A/B pairs).
-        const char* rb_s = getenv("SED_GEMM_RB");
-        const int rb_env = rb_s ? atoi(rb_s) : 8;
-        static int ncu_probe = 0;
-        if (ncu_probe == 0) {
-            int dev = 0, n = 0;
-            (void)hipGetDevice(&dev);
-            if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-            ncu_probe = n;
-        }
-        const int ncu_dev = ncu_probe;
-        const int ncu = cu_budget(ncu_dev) & ~7;   // whole XCD rounds: blockIdx.x & 7 must stay the XCD of every tile a workgroup walks
-        // Tile height: rounds of workgroups x rows per tile is what the launch costs; 224-row tiles win when they fill the last round
-        // that 256-row tiles leave mostly empty (M = 38080: 2 x 256 vs 2 x 224 for N = 768, 6 x 256 vs 6 x 224 for N = 2304).
-        const int ntn = g.N / V3_T;
-        const long long t8 = (long long)cdiv(g.M, 256) * ntn, t7 = (long long)cdiv(g.M, 224) * ntn;
-        const long long c8 = ((t8 + ncu - 1) / ncu) * 256, c7 = ((t7 + ncu - 1) / ncu) * 224;
-        const bool use7 = g.gbias == nullptr && g.k_wrap == 0 && g.k8 == 0 && (rb_env == 7 || (rb_env == 0 && c7 * 100 < c8 * 97));
-        dim3 grid3((unsigned)(use7 ? t7 : t8), 1);
-        gg.persist = (persist_env && (int)grid3.x > ncu) ? 1 : 0;
-        if (gg.persist) grid3.x = ncu;
-        {
-            // SED_GEMM_DYN (read per launch; default 1): dynamic tile walk of the persistent form, 0 = the static walk (bit-identical results)
-            const char* dy = getenv("SED_GEMM_DYN");
-            gg.tile_ctr = (gg.persist && !(dy && atoi(dy) == 0)) ? dyn_counter_slot() : nullptr;
-        }
-        gg.stagger = 0;      // (the staggered-start experiment of rounds 3 / 4 showed no effect; its environment switches are gone, the field stays reserved)
-        const GemmArgs& g = gg;
-        if (g.rowpart != nullptr || g.rowstat != nullptr) {
-            // folded LayerNorm: producer (residual epilogue) or consumer (head-split / fused-GELU epilogue); f16, no other special mode
-            if constexpr (EPI == EPI_F32_RESID || EPI == EPI_GELU || EPI == EPI_QKV) {
-                constexpr bool producer = EPI == EPI_F32_RESID;
-                if (!f16 || g.gbias != nullptr || g.k_wrap != 0 || (g.N & 63)) return SED_ERR_ARG;
-                if (producer ? (g.rowpart == nullptr || g.outH == nullptr || g.rowstat != nullptr)
-                             : (g.rowstat == nullptr || g.colS == nullptr || g.rowpart != nullptr)) return SED_ERR_ARG;
-                static bool attrl[8] = {false, false, false, false, false, false, false, false};
-#define PP_LN_LAUNCH(GBV, RBV, SLOT)                                                                                     \
-                {                                                                                                         \
-                    if (!attrl[SLOT]) { (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, true, GBV, RBV>, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS); attrl[SLOT] = true; } \
-                    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, true, GBV, RBV>), grid3, dim3(512), V3_LDS, s, g);          \
-                }
-                if constexpr (producer) {
-                    if (g.res_lo != nullptr && g.lo8 && g.out_lo != nullptr) { if (use7) PP_LN_LAUNCH(6, 7, 4) else PP_LN_LAUNCH(6, 8, 5) }
-                    else if (g.res_lo != nullptr && g.lo8) { if (use7) PP_LN_LAUNCH(7, 7, 6) else PP_LN_LAUNCH(7, 8, 7) }
-                    else if (g.res_lo != nullptr) { if (use7) PP_LN_LAUNCH(5, 7, 2) else PP_LN_LAUNCH(5, 8, 3) }
-                    else { if (use7) PP_LN_LAUNCH(3, 7, 0) else PP_LN_LAUNCH(3, 8, 1) }
-                } else {
-                    if (use7) PP_LN_LAUNCH(3, 7, 0) else PP_LN_LAUNCH(3, 8, 1)
-                }
-#undef PP_LN_LAUNCH
-                return sed_check_launch();
-            } else {
-                return SED_ERR_ARG;
-            }
-        }
-        if (g.k8 != 0) {
-            // two-term weights, lo product on the fp8 matrix path (GemmArgs.k8): the two-term variants' epilogues behind a K walk of f16
-            // tiles followed by e4m3 tiles
-            if constexpr (EPI == EPI_F32_RESID || EPI == EPI_GELU || EPI == EPI_QKV) {
-                if (!f16 || g.gbias != nullptr || g.k_wrap != 0 || g.a_slab || ((g.K / BK - g.k8) & 1) || g.k8 >= g.K / BK) return SED_ERR_ARG;
-                static bool attr9 = false;
-                if constexpr (EPI == EPI_QKV) {
-                    if (g.qt != nullptr || g.kt != nullptr || g.vt != nullptr || g.q2 != nullptr || g.q2t != nullptr || g.pu != nullptr) return SED_ERR_ARG;
-                    if (!attr9) { (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, true, 8, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS); attr9 = true; }
-                    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, true, 8, 8, true>), grid3, dim3(512), V3_LDS, s, g);
-                } else {
-                    if (!attr9) { (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, true, 2, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS); attr9 = true; }
-                    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, true, 2, 8, true>), grid3, dim3(512), V3_LDS, s, g);
-                }
-                return sed_check_launch();
-            } else {
-                return SED_ERR_ARG;
-            }
-        }
-        if (g.gbias != nullptr || g.k_wrap != 0) {
-            // row-group bias / two-term weights: evaluation-mode encoder GEMMs only (f16 operands; residual, fused-GELU and head-split epilogues)
-            if constexpr (EPI == EPI_F32_RESID || EPI == EPI_GELU || EPI == EPI_QKV) {
-                if (!f16 || (g.gbias != nullptr && g.k_wrap != 0)) return SED_ERR_ARG;
-                static bool attrg[2] = {false, false};
-                if constexpr (EPI == EPI_QKV) {
-                    // two-term weights, row-major q / k / v only (the evaluation passes of the encoder): mode 8 = the two-term K walk with the
-                    // LDS-free head-split epilogue of modes 3 / 4
-                    if (g.k_wrap != 0 && g.qt == nullptr && g.kt == nullptr && g.vt == nullptr && g.q2 == nullptr && g.q2t == nullptr && g.pu == nullptr) {
-                        static bool attr8 = false;
-                        if (!attr8) { (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS); attr8 = true; }
-                        hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, true, 8>), grid3, dim3(512), V3_LDS, s, g);
-                        return sed_check_launch();
-                    }
-                }
-                if constexpr (EPI == EPI_GELU) if (g.out_e4m3) {
-                    // row-group bias + the e4m3 image of the output (fc1 of the evaluation-mode encoder in its fp8 form: f16 weights + mean
-                    // correction, the activation leaves as fc2's two-image A operand): the F8 kernel with no fp8 K tiles
-                    if (g.k_wrap != 0 || ((g.K / BK) & 1)) return SED_ERR_ARG;
-                    static bool attrge = false;
-                    if (!attrge) { (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, true, 1, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS); attrge = true; }
-                    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, true, 1, 8, true>), grid3, dim3(512), V3_LDS, s, g);
-                    return sed_check_launch();
-                }
-                if (g.k_wrap != 0) {
-                    if (!attrg[1]) { (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS); attrg[1] = true; }
-                    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, true, 2>), grid3, dim3(512), V3_LDS, s, g);
-                } else {
-                    if (!attrg[0]) { (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS); attrg[0] = true; }
-                    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, true, 1>), grid3, dim3(512), V3_LDS, s, g);
-                }
-                return sed_check_launch();
-            } else {
-                return SED_ERR_ARG;
-            }
-        }
-        if constexpr (EPI == EPI_QKV) {
-            // the encoder's form of the head split -- row-major q / k / v, no biased second q, no transposed copies (its attention kernels
-            // transpose in LDS): a kernel without those paths (mode 4), 3 % faster than carrying them as run-time branches
-            if (g.qt == nullptr && g.kt == nullptr && g.vt == nullptr && g.q2 == nullptr && g.q2t == nullptr && g.pu == nullptr) {
-                static bool attrq[2][2] = {{false, false}, {false, false}};
-#define SED_PP_LAUNCH_Q(F, RBV)                                                                                            \
-                {                                                                                                          \
-                    if (!attrq[F][RBV - 7]) {                                                                              \
-                        (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, F, 4, RBV>, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS); \
-                        attrq[F][RBV - 7] = true;                                                                          \
-                    }                                                                                                      \
-                    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, F, 4, RBV>), grid3, dim3(512), V3_LDS, s, g);               \
-                }
-                if (f16) { if (use7) SED_PP_LAUNCH_Q(true, 7) else SED_PP_LAUNCH_Q(true, 8) }
-                else { if (use7) SED_PP_LAUNCH_Q(false, 7) else SED_PP_LAUNCH_Q(false, 8) }
-#undef SED_PP_LAUNCH_Q
-                return sed_check_launch();
-            }
-        }
-        static bool attrp[2][2] = {{false, false}, {false, false}};
-#define SED_PP_LAUNCH(F, RBV)                                                                                              \
-        {                                                                                                                  \
-            if (!attrp[F][RBV - 7]) {                                                                                      \
-                (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel<EPI, F, 0, RBV>, hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS); \
-                attrp[F][RBV - 7] = true;                                                                                  \
-            }                                                                                                              \
-            hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI, F, 0, RBV>), grid3, dim3(512), V3_LDS, s, g);                   \
-        }
-        if (f16) { if (use7) SED_PP_LAUNCH(true, 7) else SED_PP_LAUNCH(true, 8) }
-        else { if (use7) SED_PP_LAUNCH(false, 7) else SED_PP_LAUNCH(false, 8) }
-#undef SED_PP_LAUNCH
+        bool use7 = false;
+        const unsigned grid = pp_geometry(gg, use7);
+        const PpLaunch launch = pp_select<EPI>(gg, f16, use7);
+        if (launch == nullptr) return SED_ERR_ARG;
+        launch(gg, grid, s);
         return sed_check_launch();
     }
     if (g.k_wrap != 0 || g.k8 != 0 || g.rowpart != nullptr || g.rowstat != nullptr) return SED_ERR_ARG;   // 256^2-kernel-only modes (N % 256 == 0, M >= 1024)
@@ -2255,28 +2251,29 @@ static int launch_gemm(const GemmArgs& g, int f16, hipStream_t s) {
     return sed_check_launch();
 }
 
+// The fields every builder below sets the same way: operands, extents and pitches; one K split, alpha 1, every output column written
+static GemmArgs gemm_args(const void* A, const void* B, int M, int N, int K, int lda, int ldb, int ldc) {
+    GemmArgs g = {};
+    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    g.ksplit = 1; g.alpha = 1.f; g.ncols = N;
+    return g;
+}
 static int gemm_nt_impl(const void* A, const void* B, int M, int N, int K, int lda, int ldb, int epi, const float* bias,
                         const float* resF, float* outF, void* outH, void* outH2, const void* auxH, int ldc, float alpha,
                         int ksplit, int f16, int ncols, hipStream_t stream, const float* gbias = nullptr, int gb_rows = 0, int two_term = 0,
                         int f8_scale = 0, int out_e4m3 = 0) {
     (void)hipGetLastError();
-    GemmArgs g = {};
     if (out_e4m3 && ((two_term != 3 && gbias == nullptr) || epi != EPI_GELU || outH != nullptr || ldc < N + N / 2)) return SED_ERR_ARG;
-    g.out_e4m3 = out_e4m3;
-    if (two_term == 3) {      // A [M, K f16 | K e4m3] against B [N, K f16 | K e4m3]: K / 64 f16 tiles + K / 128 fp8 tiles
-        if (K % 128 || epi == EPI_ATOMIC || epi == EPI_DGELU || gbias != nullptr || ksplit > 1) return SED_ERR_ARG;
-        g.k8 = K / 128; g.f8_scale = f8_scale;
-        K += K / 2;
-    } else if (two_term) {      // A [M, K] against B [N, 2K]
-        if (K % BK || epi == EPI_ATOMIC || epi == EPI_DGELU || gbias != nullptr || ksplit > 1) return SED_ERR_ARG;
-        g.k_wrap = K / BK;
-        K *= 2;
-    }
+    if (two_term && (K % (two_term == 3 ? 128 : BK) || epi == EPI_ATOMIC || epi == EPI_DGELU || gbias != nullptr || ksplit > 1)) return SED_ERR_ARG;
     if (gbias != nullptr && (gb_rows < 128 || M % gb_rows || epi == EPI_ATOMIC || epi == EPI_DGELU)) return SED_ERR_ARG;
+    // two_term 3: A [M, K f16 | K e4m3] against B [N, K f16 | K e4m3], K / 64 f16 tiles + K / 128 fp8 tiles; else: A [M, K] against B [N, 2K]
+    GemmArgs g = gemm_args(A, B, M, N, two_term == 3 ? K + K / 2 : (two_term ? 2 * K : K), lda, ldb, ldc);
+    if (two_term == 3) { g.k8 = K / 128; g.f8_scale = f8_scale; }
+    else if (two_term) g.k_wrap = K / BK;
+    g.out_e4m3 = out_e4m3;
     g.gbias = gbias; g.gb_rows = gb_rows;
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B;
-    g.ncols = ncols;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ksplit = ksplit > 0 ? ksplit : 1;
+    g.ncols = ncols; g.ksplit = ksplit > 0 ? ksplit : 1;
     g.alpha = alpha; g.bias = bias; g.resF = resF; g.outF = outF; g.outH = (bf16_t*)outH; g.outH2 = (bf16_t*)outH2;
     g.auxH = (const bf16_t*)auxH;
     g.bwd_bf16 = (f16 & 2) ? 1 : 0;
@@ -2347,9 +2344,7 @@ static int gemm_nt_lnp_impl(const void* A, const void* B, int M, int N, int K, i
     if (N % 256 || M < 1024 || K % BK || x16 == nullptr || rowpart == nullptr || ldc != N) return SED_ERR_ARG;
     // residual: fp32 resF, or the planes res_hi + res_lo; result: fp32 outF + f16 image x16, or the planes x16 (hi) + out_lo
     if ((res_lo != nullptr) != (res_hi != nullptr) || (res_lo == nullptr && resF == nullptr) || (out_lo == nullptr && outF == nullptr)) return SED_ERR_ARG;
-    GemmArgs g = {};
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.ncols = N;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ksplit = 1; g.alpha = 1.f;
+    GemmArgs g = gemm_args(A, B, M, N, K, lda, ldb, ldc);
     g.bias = bias; g.resF = resF; g.outF = outF; g.outH = (bf16_t*)x16; g.rowpart = rowpart;
     g.auxH = (const bf16_t*)res_hi; g.res_lo = (const bf16_t*)res_lo; g.out_lo = (bf16_t*)out_lo; g.lo8 = lo8;
     if (lo8 && lda == 64 && K > 64) { g.a_slab = 1; g.lda = K; }      // A as [K / 64][M][64] (what sed_gemm_nt_lnc8 writes with ldc = 64)
@@ -2372,9 +2367,7 @@ static int gemm_nt_lnc_impl(const void* A, const void* B, int M, int N, int K, i
                             const float* rowstat, void* outH2, int ldc, int a_slab, hipStream_t stream) {
     (void)hipGetLastError();
     if (N % 256 || M < 1024 || K % BK || colS == nullptr || rowstat == nullptr || outH2 == nullptr) return SED_ERR_ARG;
-    GemmArgs g = {};
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.ncols = N;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ksplit = 1; g.alpha = 1.f;
+    GemmArgs g = gemm_args(A, B, M, N, K, lda, ldb, ldc);
     g.bias = colC; g.outH2 = (bf16_t*)outH2; g.colS = colS; g.rowstat = rowstat; g.a_slab = a_slab;
     if (a_slab && (lda != K || (size_t)M * K * 2 >= (1ull << 31))) return SED_ERR_ARG;
     if (a_slab && ldc == 64 && N > 64) { g.c_slab = 1; g.ldc = N; }      // output as [N / 64][M][64]
@@ -2427,9 +2420,7 @@ static int gemm_qkv_lnc_impl(const void* A, const void* W, const float* colC, co
                              int heads, int seq, int seq_pad, void* q, void* k, void* v, int a_slab, hipStream_t stream) {
     (void)hipGetLastError();
     if (M < 1024 || K % BK || colS == nullptr || rowstat == nullptr || seq <= 0 || (seq_pad % 64) || M % seq) return SED_ERR_ARG;
-    GemmArgs g = {};
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)W;
-    g.M = M; g.N = 3 * heads * 64; g.K = K; g.lda = K; g.ldb = K; g.ldc = g.N; g.ksplit = 1; g.alpha = 1.f; g.ncols = g.N;
+    GemmArgs g = gemm_args(A, W, M, 3 * heads * 64, K, K, K, 3 * heads * 64);
     g.bias = colC; g.colS = colS; g.rowstat = rowstat;
     g.q = (bf16_t*)q; g.k = (bf16_t*)k; g.v = (bf16_t*)v;
     g.seq = seq; g.seq_pad = seq_pad; g.heads = heads; g.a_slab = a_slab;
@@ -2464,11 +2455,9 @@ static int gemm_qkv_impl(const void* A, const void* W, const float* bias, int M,
                          void* q2t, const float* pos_u, const float* pos_v, int f16, const float* gbias, int gb_rows, hipStream_t stream, int two_term,
                          int f8_scale) {
     (void)hipGetLastError();
-    GemmArgs g = {};
     if (gbias != nullptr && (gb_rows < 128 || M % gb_rows)) return SED_ERR_ARG;
+    GemmArgs g = gemm_args(A, W, M, 3 * heads * 64, K, K, K, 3 * heads * 64);
     g.gbias = gbias; g.gb_rows = gb_rows;
-    g.A = (const bf16_t*)A; g.B = (const bf16_t*)W;
-    g.M = M; g.N = 3 * heads * 64; g.K = K; g.lda = K; g.ldb = K; g.ldc = g.N; g.ksplit = 1; g.alpha = 1.f;
     if (two_term == 3) {
         if (K % 128 || gbias != nullptr) return SED_ERR_ARG;
         g.k8 = K / 128; g.f8_scale = f8_scale; g.K = K + K / 2; g.lda = g.K; g.ldb = g.K;
@@ -2477,7 +2466,6 @@ static int gemm_qkv_impl(const void* A, const void* W, const float* bias, int M,
         g.k_wrap = K / BK; g.K = 2 * K; g.ldb = 2 * K;
         if (two_term == 2) { g.ldb = 3 * K; g.b_skip = K / BK; }      // W = [hi | hi | lo]: walk hi, then lo
     }
-    g.ncols = g.N;
     g.bias = bias;
     g.q = (bf16_t*)q; g.k = (bf16_t*)k; g.v = (bf16_t*)v; g.qt = (bf16_t*)qt; g.kt = (bf16_t*)kt; g.vt = (bf16_t*)vt;
     g.q2 = (bf16_t*)q2; g.q2t = (bf16_t*)q2t; g.pu = pos_u; g.pv = pos_v;

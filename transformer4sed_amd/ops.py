@@ -158,15 +158,54 @@ class plain_precision:
         ALG_K_SCALE = self.prev
 
 
+def _epi_out(by_epi):      # output + side-input bytes per element by epilogue (args[7]); fused GELU (3): 2 per f16 output present (outH, outH2)
+    return lambda a: 2 * ((a[11] is not None) + (a[12] is not None)) if a[7] == 3 else by_epi.get(a[7], 4)
+
+
+def _lnp_out(pl):      # folded-LayerNorm producer: residual read (fp32 4 B, planes pl B if res_lo) + result (fp32 + f16 image 6 B, planes pl B if out_lo)
+    return lambda a: (pl if a[10] is not None else 4) + (pl if a[13] is not None else 6)
+
+
+def _qkv_nout(a):
+    return sum(x is not None for x in a[8:16])
+
+
+_NT_OUT, _W2_OUT = _epi_out({0: 4, 1: 8, 2: 2, 4: 4, 5: 8, 7: 6, 8: 6}), _epi_out({1: 8})
+# The GEMM entry points of the kernel timer, by the argument order of their C signatures (include/sed_hip.h).  Per row:
+#   layout, i: "nt": (M, N, K) = args[i:i + 3]; "qkv": (M, K, heads) = args[i:i + 3], N = 3 * heads * 64; "tn": (T, M, N), K = T
+#   operand bytes (ab, wn): ab * K * (M + wn * N) -- 2 B halves, 3 B for the [f16 | e4m3] rows; wn = 2: two-term weight image [N, 2K]
+#   out: output + side-input bytes per element of [M, N] ("qkv": of one output [M, N / 3]), a number or a function of args; None: no bytes
+#   tag: the shape tag of tools/gemm_shapes.py ({epi} = args[7], {nout} = outputs present among q .. q2t); None: no shape row
+_GEMM = {
+    "sed_gemm_nt":         ("nt", 2, (2, 1), _NT_OUT, "epi{epi}"),
+    "sed_gemm_nt_gb":      ("nt", 2, (2, 1), _NT_OUT, "epi{epi}gb"),
+    "sed_gemm_nt_gb_e4m3": ("nt", 2, (2, 1), None, None),
+    "sed_gemm_nt_w2":      ("nt", 2, (2, 2), _W2_OUT, "epi{epi}w2"),      # (FLOPs: the logical 2 M N K, half of the MFMA FLOPs issued)
+    "sed_gemm_nt_w2f8":    ("nt", 2, (3, 1), _W2_OUT, "epi{epi}w2f8"),
+    "sed_gemm_nt_lnp":     ("nt", 2, (2, 1), _lnp_out(4), "epi1lnp"),
+    "sed_gemm_nt_lnp8":    ("nt", 2, (2, 1), _lnp_out(3), "epi1lnp"),
+    "sed_gemm_nt_lnc":     ("nt", 2, (2, 1), 2, "epi3lnc"),
+    "sed_gemm_nt_lnc8":    ("nt", 2, (2, 1), 2, "epi3lnc"),
+    "sed_gemm_qkv_lnc":    ("qkv", 5, (2, 1), 6, "qkv3lnc"),
+    "sed_gemm_qkv_lnc8":   ("qkv", 5, (2, 1), 6, "qkv3lnc"),
+    "sed_gemm_qkv":        ("qkv", 3, (2, 1), lambda a: 2 * _qkv_nout(a), "qkv{nout}"),
+    "sed_gemm_qkv_w2s":    ("qkv", 3, (2, 2), lambda a: 2 * _qkv_nout(a), "qkv{nout}w2s"),
+    "sed_gemm_qkv_gb":     ("qkv", 3, (2, 1), 6, "qkv3gb"),
+    "sed_gemm_qkv_w2":     ("qkv", 3, (2, 2), 6, "qkv3w2"),
+    "sed_gemm_qkv_w2f8":   ("qkv", 3, (3, 1), 6, "qkv3w2f8"),
+    "sed_gemm_dw_tn":      ("tn", 3, (2, 1), 8, "tn"),
+}
+
+
+def _gemm_mnk(row, args):
+    a, b, c = args[row[1]:row[1] + 3]
+    return (a, b, c) if row[0] == "nt" else (a, 3 * c * 64, b) if row[0] == "qkv" else (b, c, a)
+
+
 def _flops_of(name, args):
-    if name in ("sed_gemm_nt", "sed_gemm_nt_gb", "sed_gemm_nt_gb_e4m3", "sed_gemm_nt_w2", "sed_gemm_nt_w2f8", "sed_gemm_nt_lnp", "sed_gemm_nt_lnp8", "sed_gemm_nt_lnc", "sed_gemm_nt_lnc8"):       # (w2: the logical 2 M N K, half of the MFMA FLOPs issued)
-        return 2.0 * args[2] * args[3] * args[4]
-    if name in ("sed_gemm_qkv_lnc", "sed_gemm_qkv_lnc8"):
-        return 2.0 * args[5] * args[6] * (3 * args[7] * 64)
-    if name in ("sed_gemm_qkv", "sed_gemm_qkv_gb", "sed_gemm_qkv_w2", "sed_gemm_qkv_w2f8", "sed_gemm_qkv_w2s"):
-        return 2.0 * args[3] * args[4] * (3 * args[5] * 64)
-    if name == "sed_gemm_dw_tn":
-        return 2.0 * args[3] * args[4] * args[5]
+    if name in _GEMM:
+        M, N, K = _gemm_mnk(_GEMM[name], args)
+        return 2.0 * M * N * K
     if name == "sed_gemm_f32_nt":                # (A, B, bias, R, C, M, N, K, lda, ldb, ldc, batch, ...): fp32-input MFMA, its own roofline
         return 2.0 * args[5] * args[6] * args[7] * args[11]
     if name == "sed_gemm_f32":                   # (A, B, bias, R, C, pre, M, N, K, lda, ldb, ldc, transA, transB, batch, ...)
@@ -182,59 +221,20 @@ def _flops_of(name, args):
 
 def _shape_of(name, args):
     """(M, N, K, epilogue / output count) of one GEMM launch, for per-shape tables (tools/gemm_shapes.py)."""
-    if name in ("sed_gemm_nt", "sed_gemm_nt_gb"):
-        return (args[2], args[3], args[4], "epi%d" % args[7] + ("gb" if name.endswith("_gb") else ""))
-    if name in ("sed_gemm_qkv_gb", "sed_gemm_qkv_w2"):
-        return (args[3], 3 * args[5] * 64, args[4], "qkv3" + name[-2:])
-    if name == "sed_gemm_qkv_w2f8":
-        return (args[3], 3 * args[5] * 64, args[4], "qkv3w2f8")
-    if name in ("sed_gemm_nt_w2", "sed_gemm_nt_w2f8"):
-        return (args[2], args[3], args[4], "epi%d" % args[7] + name[12:])
-    if name in ("sed_gemm_nt_lnp", "sed_gemm_nt_lnp8", "sed_gemm_nt_lnc", "sed_gemm_nt_lnc8"):
-        return (args[2], args[3], args[4], "epi3lnc" if "lnc" in name else "epi1lnp")
-    if name in ("sed_gemm_qkv_lnc", "sed_gemm_qkv_lnc8"):
-        return (args[5], 3 * args[7] * 64, args[6], "qkv3lnc")
-    if name in ("sed_gemm_qkv", "sed_gemm_qkv_w2s"):
-        return (args[3], 3 * args[5] * 64, args[4], "qkv%d" % sum(a is not None for a in args[8:16]) + ("w2s" if name.endswith("w2s") else ""))
-    if name == "sed_gemm_dw_tn":
-        return (args[4], args[5], args[3], "tn")
-    return None
+    row = _GEMM.get(name)
+    if row is None or row[4] is None:
+        return None
+    return _gemm_mnk(row, args) + (row[4].format(epi=args[7], nout=_qkv_nout(args)),)
 
 
 def _bytes_of(name, args):
     """Algorithmic HBM bytes of one GEMM launch: operands once + every output / side input once."""
-    if name in ("sed_gemm_qkv_gb", "sed_gemm_qkv_w2", "sed_gemm_qkv_w2f8"):
-        M, K, D = args[3], args[4], args[5] * 64
-        if name.endswith("f8"):
-            return 3.0 * K * (M + 3 * D) + 2.0 * M * D * 3
-        return 2.0 * K * (M + 3 * D * (2 if name.endswith("w2") else 1)) + 2.0 * M * D * 3
-    if name in ("sed_gemm_nt_lnp", "sed_gemm_nt_lnp8"):
-        # operands + the residual read (fp32 4 B / f16 planes 4 B / f16 + byte planes 3 B) + fp32 and f16 image (6 B) or the two planes (4 B / 3 B)
-        M, N, K = args[2], args[3], args[4]
-        pl = 3.0 if name.endswith("8") else 4.0
-        return 2.0 * K * (M + N) + ((pl if args[10] is not None else 4.0) + (pl if args[13] is not None else 6.0)) * M * N
-    if name in ("sed_gemm_nt_lnc", "sed_gemm_nt_lnc8"):
-        M, N, K = args[2], args[3], args[4]
-        return 2.0 * K * (M + N) + 2.0 * M * N
-    if name in ("sed_gemm_qkv_lnc", "sed_gemm_qkv_lnc8"):
-        M, K, D = args[5], args[6], args[7] * 64
-        return 2.0 * K * (M + 3 * D) + 2.0 * M * D * 3
-    if name in ("sed_gemm_nt_w2", "sed_gemm_nt_w2f8"):
-        M, N, K, epi = args[2], args[3], args[4], args[7]
-        out = {1: 8, 3: 2 * ((args[11] is not None) + (args[12] is not None))}.get(epi, 4)
-        return (3.0 * K * (M + N) if name.endswith("f8") else 2.0 * K * (M + 2 * N)) + float(out) * M * N
-    if name in ("sed_gemm_nt", "sed_gemm_nt_gb"):
-        M, N, K, epi = args[2], args[3], args[4], args[7]
-        out = {0: 4, 1: 8, 2: 2, 3: 2 * ((args[11] is not None) + (args[12] is not None)), 4: 4, 5: 8, 7: 6, 8: 6}.get(epi, 4)
-        return 2.0 * K * (M + N) + float(out) * M * N
-    if name in ("sed_gemm_qkv", "sed_gemm_qkv_w2s"):
-        M, K, D = args[3], args[4], args[5] * 64
-        nout = sum(a is not None for a in args[8:16])
-        return 2.0 * K * (M + 3 * D * (2 if name.endswith("w2s") else 1)) + 2.0 * M * D * nout
-    if name == "sed_gemm_dw_tn":
-        T, M, N = args[3], args[4], args[5]
-        return 2.0 * T * (M + N) + 8.0 * M * N
-    return 0.0
+    row = _GEMM.get(name)
+    if row is None or row[3] is None:
+        return 0.0
+    M, N, K = _gemm_mnk(row, args)
+    (ab, wn), out = row[2], row[3](args) if callable(row[3]) else row[3]
+    return float(ab) * K * (M + wn * N) + float(out) * M * (N // 3 if row[0] == "qkv" else N)
 
 
 def _hbm_bytes_of(name, args):
