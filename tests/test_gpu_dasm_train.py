@@ -1,6 +1,7 @@
 """Training kernels of the DASM / AudioSet-Strong path (csrc/dasm.hip, transformer4sed_amd/dasm.py) against torch fp32 / fp64 autograd on
 the CPU: the general fp32 GEMM (all three products of a Linear, batched einsum forms, dropout epilogue), the cross / self attention
-backward (mask, dropout with the kernels' own counter-based bits dumped through sed_dropout_f32), the dual-stream finish backward, the
+backward (mask, dropout with the kernels' own counter-based bits dumped through sed_dropout_f32 and held to their host restatement,
+tests/dropout_cases.py), the dual-stream finish backward, the
 supervised-loss kernel, the closed-set head for 407 classes, and the whole query decoder + head forward / backward against
 oracle/dasm_oracle.py under autograd (weights, frame tokens, SED decoder output; with and without dropout)."""
 import os
@@ -14,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import dropout_cases  # noqa: E402
 from transformer4sed_amd import synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +39,11 @@ def keep_mask(n, p, seed, site):
     from transformer4sed_amd.ops import call
     m = torch.empty(n, dtype=torch.uint8, device=DEV)
     call("sed_dropout_f32", None, None, m, n, float(p), int(seed), int(site))
-    return m.cpu()
+    m = m.cpu()
+    # the dump equals the host restatement of the bit function (tests/dropout_cases.py): every consumer test below that injects this mask
+    # into its oracle is thereby a test against an independent reference, not only of the consumers' agreement with each other
+    assert torch.equal(m, torch.from_numpy(dropout_cases.dasm_keep(n, float(p), int(seed), int(site))))
+    return m
 
 
 def test_gemm_f32_all_forms_vs_torch():
@@ -400,6 +406,37 @@ def test_dasm_head_forward_backward_vs_oracle_autograd(B, P, T, Q, pdrop, extern
     assert not bad, bad
 
 
+def test_dasm_head_train_mode_without_saving_drops_at_all_six_sites():
+    """Train mode under torch.no_grad() (`save=False, train=True`: a mean-teacher's teacher pass): the same dropout as a saving forward -- all
+    six sites of both layers, bits of `drop_seed` -- against oracle/dasm_oracle.py (fp64) with the host reference's masks
+    (tests/dropout_cases.py) injected at every site.  (Before the fix the attention probabilities, sites 0 and 2, went undropped.)"""
+    from oracle import dasm_oracle
+    B, P, T, Q, pdrop, seed = 2, 60, 60, 12, 0.1, 0x0123456789ABCDEF
+    head, sd = _head(8, 1024, 2)
+    head.dropout = pdrop
+    frame = torch.from_numpy(synth.det_uniform("dasm_tr/frame", (B, P, 768), -1.5, 1.5))
+    x_dec = torch.from_numpy(synth.det_normal("dasm_tr/xdec", (B, T, 768))) * 0.5
+    ext = torch.from_numpy(synth.det_normal("dasm_tr/q", (Q, 1024)))
+    ext = ext / ext.norm(dim=-1, keepdim=True)
+    tmask = dasm_oracle.att_mask(Q, max(1, Q // 2))
+    pad = torch.zeros(B, T, dtype=torch.bool)
+    pad[0, T - 7:] = True
+    with torch.no_grad():
+        s, w, a, mf = head.forward(frame.to(DEV), x_dec.to(DEV), query=ext.to(DEV), tgt_mask=tmask, temp_w=0.5, pad_mask=pad, save=False, train=True,
+                                   drop_seed=seed)
+    H, Dd = 12, 768
+    drops = {"p": pdrop}
+    for l in range(2):
+        for site, shape in ((0, (B, H, Q, P)), (1, (B, Q, Dd)), (2, (B, H, Q, Q)), (3, (B, Q, Dd)), (4, (B, Q, Dd)), (5, (B, Q, Dd))):
+            drops[(l, site)] = torch.from_numpy(dropout_cases.dasm_keep(int(np.prod(shape)), pdrop, seed, 8 * l + site)).view(shape).double()
+    sdd = {k: v.double() for k, v in sd.items()}
+    so, wo, ao, mo = dasm_oracle.dasm_head(sdd, frame.double(), x_dec.double(), query=ext.double(), tgt_mask=tmask, temp_w=0.5, pad_mask=pad, n_layers=2,
+                                           drops=drops)
+    e_s, e_w, e_a = (float((got.cpu().double() - ref).abs().max()) for got, ref in ((s, so), (w, wo), (a, ao)))
+    logerr(f"dasm head, train mode without saving, p={pdrop}: strong {e_s:.2e} weak {e_w:.2e} tagging {e_a:.2e} (bounds 1e-4, 1e-4, 1e-5)")
+    assert e_s < 1e-4 and e_w < 1e-4 and e_a < 1e-5, (e_s, e_w, e_a)
+
+
 # ---------------------------------------------------------------------------------------------------------------------- whole model
 CNN = dict(n_in_channel=1, activation="cg", conv_dropout=0.0, kernel_size=[3] * 10, padding=[1] * 10, stride=[1] * 10,
            nb_filters=list(synth.PMAM_FILTERS), pooling=[list(p) for p in synth.PMAM_POOLING])
@@ -559,6 +596,37 @@ def test_dasm_train_mode_dropout_multimodal_and_external_query_grad():
         assert s_t.shape == (2, 8, 1000)
         with pytest.raises(RuntimeError):
             net2(mel, temp_w=0.5, query=torch.from_numpy(sd["at_query"]).to(DEV))
+
+
+def test_dasm_train_mode_under_no_grad_draws_fresh_dropout_bits():
+    """A train-mode forward under torch.no_grad() (what a mean-teacher's teacher pass is) takes a fresh dropout seed like a forward that
+    saves for the backward: two forwards differ, the same generator state repeats the first; eval mode has no dropout and leaves the
+    model's seed generator where it was."""
+    net = build_dasm(2, dropout=0.1).train()
+    mel = torch.from_numpy(synth.det_uniform("dasm_tr/mel", (2, 128, 1000), -1.2, 1.2)).to(DEV)
+    tol = 5e-4            # (the order of the trunk's fp32 atomics at temperature 0.5, as in the test above)
+    with torch.no_grad():
+        torch.manual_seed(3)
+        s1 = net(mel, temp_w=0.5)[0].clone()
+        s2 = net(mel, temp_w=0.5)[0].clone()
+        net._drop_gen = None
+        torch.manual_seed(3)
+        s3 = net(mel, temp_w=0.5)[0].clone()
+        same, other = float((s1 - s3).abs().max()), float((s1 - s2).abs().max())
+        print("no_grad train mode: same seed", same, "other seed", other)
+        assert other > 0
+        assert same < tol, same
+        assert other > 20 * tol, other
+        # what differs between two forwards is the head's dropout and nothing else: without it they agree
+        net.at_dropout = 0.0
+        assert float((net(mel, temp_w=0.5)[0] - net(mel, temp_w=0.5)[0]).abs().max()) < tol
+        net.at_dropout = 0.1
+        net.eval()
+        state = net._drop_gen.get_state().clone()
+        e1 = net(mel, temp_w=0.5)[0].clone()
+        e2 = net(mel, temp_w=0.5)[0].clone()
+        assert float((e1 - e2).abs().max()) < tol
+        assert torch.equal(net._drop_gen.get_state(), state)
 
 
 def test_audioset_strong_trainer_steps_vs_reference_trainer(golden):

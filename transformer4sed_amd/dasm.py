@@ -288,7 +288,9 @@ class DasmHead:
                 drop_seed=0):
         """frame_tokens [B, P, 768] fp32 (the backbone's final-norm patch tokens, cls / dist tokens removed); x_dec [B, T, Dd] fp32 (SED
         decoder output); query [Q, query_dim] external embeddings (None: the learned `at_query`; a list: one tensor per modality);
-        tgt_mask [Q, Q] bool, True = masked.  train: dropout of the decoder layers active (p = self.dropout, bits from `drop_seed`).
+        tgt_mask [Q, Q] bool, True = masked.  train: dropout of the decoder layers active at all six sites of every layer (p = self.dropout),
+        whether or not `save`; its bits are a function of `drop_seed`, the site and the element index alone, so the caller hands a fresh
+        seed to every train-mode forward (a repeated seed repeats the mask).  train=False ignores `drop_seed`.
         -> strong [B, Q, T], weak [B, Q], at_out [B, Q], mask_feat [B, Q, Dd]  (+ ctx when save)."""
         P, L, H, Dd, dh = self.P, self.L, self.H, self.Dd, self.dh
         dev = frame_tokens.device
@@ -297,9 +299,11 @@ class DasmHead:
         frame_tokens = frame_tokens.contiguous().float()
         x_dec = x_dec.contiguous().float()
         E = lambda *s: torch.empty(*s, dtype=F32, device=dev)
-        S = (lambda *s: E(*s)) if save else (lambda *s: None)
         pdrop = self.dropout if train else 0.0
         D_ = lambda site: (pdrop, drop_seed, site) if pdrop > 0 else NO_DROP
+        # attention with dropout on its probabilities is the training kernel's (it wants somewhere to put the row log-sum-exps): a train-mode
+        # pass that saves nothing -- a mean-teacher's forward under no_grad -- drops at all six sites of a layer like a saving one
+        L_ = E if (save or pdrop > 0) else (lambda *s: None)
         # ---- memory side: K / V of every layer from the patch tokens, one GEMM
         wkv, bkv, wkv_raw = self._memory_weights(cache=not save)
         ldkv = 2 * L * Dd
@@ -332,8 +336,8 @@ class DasmHead:
             qc, c_q = self._lin(x, pre + "multihead_attn.in_proj", N=Dd, save=save, packed=True)      # rows 0 .. Dd-1 of the packed in_proj = W_q
             oc = E(M, Dd)
             kp = KV.data_ptr() + 4 * (2 * l * Dd)           # column blocks of the packed projection, read in place (ld = 2 L Dd)
-            lse_c = S(B * H * Q)
-            if save:
+            lse_c = L_(B * H * Q)
+            if save or pdrop > 0:
                 call("sed_xattn_f32_fwd_train", qc, kp, kp + 4 * Dd, oc, None, lse_c, B, H, Q, Pn, dh, Dd, ldkv, ldkv, Dd, Q * Dd, *D_(8 * l + 0))
             else:
                 call("sed_xattn_f32_fwd", qc, kp, kp + 4 * Dd, oc, None, B, H, Q, Pn, dh, Dd, ldkv, ldkv, Dd, Q * Dd)
@@ -342,8 +346,8 @@ class DasmHead:
             # self attention among the queries (tgt_mask: the open-vocabulary mask)
             qkv, c_qkv = self._lin(x1, pre + "self_attn.in_proj", save=save, packed=True)                 # [M, 3 Dd]
             osf = E(M, Dd)
-            lse_s = S(B * H * Q)
-            if save:
+            lse_s = L_(B * H * Q)
+            if save or pdrop > 0:
                 call("sed_xattn_f32_fwd_train", qkv, qkv.data_ptr() + 4 * Dd, qkv.data_ptr() + 8 * Dd, osf, mask8, lse_s, B, H, Q, Q, dh, 3 * Dd, 3 * Dd,
                      3 * Dd, Dd, Q * 3 * Dd, *D_(8 * l + 2))
             else:

@@ -528,7 +528,7 @@ class PmamEngine(SedEngine):
             m._last_x_dec = xd            # (kept for tests / inspection: the SED decoder's output that sed_head reads)
             dc = m.__dict__["_dasm_call"]
             hd = dasm.forward(ft, xd, query=dc["query"], tgt_mask=dc["tgt_mask"], temp_w=float(temp_w), pad_mask=pad_mask,
-                              query_type=dc["query_type"], save=save, train=bool(m.training), drop_seed=m._next_drop_seed() if (save and m.training) else 0)
+                              query_type=dc["query_type"], save=save, train=bool(m.training), drop_seed=m._next_drop_seed() if m.training else 0)
             out["strong"], out["weak"], out["at_out"] = hd[0], hd[1], hd[2]
             hctx = hd[4] if save else None
             if save:
