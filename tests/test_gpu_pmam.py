@@ -448,3 +448,59 @@ def test_pmam_finetune_trainer_steps_vs_reference_trainer(golden):
             worst = max(worst, ms)
             assert ms < 0.15 and me < 0.15, (step, n, ms, me)
         report(f"PMAM finetune trainer step {step} worst probe mean|dp|/lr", worst)
+
+
+def _hook_stages(net, mel, **kw):
+    """Stage sequence the engine's backward reports to the gradient-ready hook (ddp.GradReducer's) for one forward / backward."""
+    stages = []
+    net._grad_ready_hook = stages.append
+    net.train()
+    out = net(mel, **kw)
+    out[0].sum().backward()
+    net._grad_ready_hook = None
+    return stages
+
+
+def test_backward_stage_hook_order_pmam_and_windows():
+    """The order of the stage hooks is what ddp.GradReducer buckets by.  PMAM with only block 1's LoRA factors trainable in the encoder
+    and the embedding frozen: the walk stops above block 0 and still ends with "embed".  MAT-SED engine with sliding windows: the window
+    groups' encoder passes fire nothing, the global pass fires every stage once."""
+    mel = torch.from_numpy(synth.det_uniform("pmam_d2/mel", (2, 128, 1000), -1.2, 1.2)).cuda()
+    net = build(2, 2, dropout=0.0)
+    for n, p in net.named_parameters():
+        if n.startswith("backbone."):
+            p.requires_grad_(n.startswith("backbone.blocks.1.") and ".lora_" in n)
+    assert _hook_stages(net, mel, encoder_win=False) == ["decoder", "heads", ("block", 1), "embed"]
+
+    from transformer4sed_amd.passt_sed import PaSST_SED
+    net = PaSST_SED(passt_feature_layer=2, f_pool="mean_pool", decode_ratio=10, at_adapter=True, decoder="transformerXL", decoder_layer_num=3,
+                    decoder_pos_emd_len=1000, load_pretrained_model=False, encoder_depth=2)
+    sd = synth.matsed_state_dict_np(tag="w768", depth=12, mlm=False)
+    own = net.state_dict()
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items() if k in own}, strict=True)
+    stages = _hook_stages(net.cuda(), mel, encoder_win=True, mix_rate=0.5, win_param=[512, 49], temp_w=1)
+    assert stages == ["decoder", "heads", ("block", 1), ("block", 0), "embed"]
+
+
+def test_pmam_window_forward_refuses_to_save_before_any_launch(monkeypatch):
+    """No PMAM config needs the gradient through the sliding windows: forward(encoder_win=True, save=True) says so before it launches
+    anything."""
+    from transformer4sed_amd import engine, ops, pmam_engine
+    net = build_ft()
+    net.engine = net._make_engine()
+    mel = torch.from_numpy(synth.det_uniform("pmam_ft_d2/mel", (2, 128, 1000), -1.2, 1.2)).cuda()
+    seen = []
+    real = ops.call
+
+    def recording(name, *args):
+        seen.append(name)
+        return real(name, *args)
+    for mod in (ops, engine, pmam_engine):
+        monkeypatch.setattr(mod, "call", recording)
+    with pytest.raises(NotImplementedError):
+        net.engine.forward(mel, encoder_win=True, save=True)
+    assert seen == []
+    with torch.no_grad():
+        net.eval()
+        net(mel, encoder_win=True, win_param=[512, 49])      # (the recorder does see the no-grad window pass)
+    assert "sed_window_mix" in seen

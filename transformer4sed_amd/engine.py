@@ -736,75 +736,41 @@ class SedEngine:
         return cur.view(B, T, D), ctx
 
     # ------------------------------------------------------------------ full forward
+    # `forward` and `_backward_impl` are the only whole-model drivers: each is a fixed sequence of stages, and a model variant (the
+    # PMAM / DASM engine) overrides stages, never the drivers.  DESIGN.md lists the stages and both forms of each.
     def forward(self, mel, encoder_win=False, mix_rate=0.5, win_param=(512, 49), temp_w=1.0, pad_mask=None,
-                mlm_plan=None, toffsets=None, rows=None, save=False):
+                mlm_plan=None, toffsets=None, rows=None, save=False, drop_masks=None):
         """`rows`: structured frequency patchout (passt.py:533-547) -- the kept frequency rows of every backbone call of this forward
-        as lists of ints, the global pass first, then one set per sliding window in sweep order; None: nothing is dropped."""
+        as lists of ints, the global pass first, then one set per sliding window in sweep order; None: nothing is dropped.
+        `drop_masks`: injected dropout keep-masks of the CNN branch (PMAM)."""
         m = self.m
         dev = mel.device
         if mel.dtype != F32 or not mel.is_contiguous():
             mel = mel.contiguous().float()
         B, Fm, T = mel.shape
         assert Fm == 128
+        # what the stages read of this call; `win`: the sliding-window sweep or None
+        opt = dict(win=dict(mix=float(mix_rate), param=win_param, toffsets=toffsets) if encoder_win else None, rows=rows, F=12,
+                   rows_dev=None, drop_masks=drop_masks, temp_w=temp_w, pad_mask=pad_mask)
+        self._check_forward(T, opt, save)
         W = self._weights(need_t=save)
         lease = self._lease(save)
         out = {}
-        tp = (T - 16) // 10 + 1
-        tp = min(tp, 99)
-        F, rows_dev = 12, None
+        tp = min((T - 16) // 10 + 1, 99)
         if rows is not None:
-            F = len(rows[0])
-            n_sets = 1 + (len(window_starts(T, win_param[0], win_param[1])) if encoder_win else 0)
-            # (checked on the host: the kernels index the mel rows and the frequency table with these values)
-            if len(rows) != n_sets or not 1 <= F <= 12 or any(
-                    len(r) != F or min(r) < 0 or max(r) >= 12 or any(a >= b for a, b in zip(r, r[1:])) for r in rows):
-                raise ValueError(f"rows: expected {n_sets} sets of equally many strictly increasing frequency rows in [0, 12), got {rows!r}")
-            rows_dev = h2d(rows, torch.int32, dev)      # [1 + windows, F]: one upload for every row set of this forward
-        pooled, frame16, ectx = self._encoder_fwd(W, mel, [0], tp, [0], save, want_frame=m.has_at,
-                                                  rows=None if rows is None else [rows_dev[0]], F=F)
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        ratio = m.decode_ratio
-        pad = 1  # 99 -> 100 frames (passt_sed.py:258)
-        Tdec = (tp + pad) * ratio
-        assert Tdec == 1000, "MAT-SED expects 1000 decoder frames (passt_sed.py:260)"
-        xg = E(B, Tdec, D)
-        call("sed_interp_fwd", pooled, xg, B, tp, pad, ratio)
-        wctx = None
-        if encoder_win:
-            win, step = win_param
-            starts = window_starts(T, win, step)
-            if toffsets is None:
-                toffsets = [0] * len(starts)
-            # group the windows by their number of time patches (the last slab of a sweep can be shorter:
-            # min(left + win, T) - left frames, encoder_slide_window.py:28) and fold each group into the batch
-            groups = {}
-            for wi, left in enumerate(starts):
-                width = min(left + win, T) - left
-                groups.setdefault((width - 16) // 10 + 1, []).append(wi)
-            lefts, tps, offs, chunks, row = [0] * len(starts), [0] * len(starts), [0] * len(starts), [], 0
-            wgroups = []
-            for tpw, wis in groups.items():
-                pw, _, gctx = self._encoder_fwd(W, mel, [starts[w] for w in wis], tpw, [toffsets[w] for w in wis], save,
-                                                want_frame=False, rows=None if rows is None else [rows_dev[1 + w] for w in wis], F=F)
-                chunks.append(pw.view(-1, D))
-                wgroups.append(dict(ectx=gctx, row0=row, rows=len(wis) * B * tpw))
-                for k, w in enumerate(wis):
-                    lefts[w], tps[w], offs[w] = round(starts[w] * (Tdec / T)), tpw, row + k * B * tpw
-                row += len(wis) * B * tpw
-            packed = chunks[0] if len(chunks) == 1 else torch.cat(chunks, 0)
-            wdesc = h2d([lefts, tps, offs], torch.int32, dev)       # one upload for the three window tables
-            wl, wt, wo = wdesc[0], wdesc[1], wdesc[2]
-            call("sed_window_mix", packed, wl, wt, wo, len(starts), xg, float(mix_rate), B, Tdec, ratio)
-            if save:
-                wctx = dict(groups=wgroups, lefts=wl, tps=wt, offs=wo, n=len(starts), mix=float(mix_rate), rows=row)
+            opt["F"] = len(rows[0])
+            opt["rows_dev"] = h2d(rows, torch.int32, dev)      # [1 + windows, F]: one upload for every row set of this forward
+        pooled, frame16, ectx = self._encoder_fwd(W, mel, [0], tp, [0], save, want_frame=m.has_at or getattr(m, "dasm_head", None) is not None,
+                                                  rows=None if rows is None else [opt["rows_dev"][0]], F=opt["F"])
+        Tdec = (tp + 1) * m.decode_ratio      # 99 -> 100 frames (passt_sed.py:258)
+        xg, tctx = self._trunk_fwd(W, mel, pooled, tp, Tdec, opt, save)
         out["frame_before_mask"] = xg
         dec_in = xg
-        if m.mlm and mlm_plan is not None:
-            out["mask_id_seq"] = mlm_plan["mask_ids"]
-            if mlm_plan["effective"]:
-                dec_in = E(B, Tdec, D)
-                call("sed_mlm_apply", xg, self.P("mask_token").reshape(D), mlm_plan["action"], mlm_plan["src_idx"],
-                     dec_in, B * Tdec)
+        plan = mlm_plan if (m.mlm and mlm_plan is not None) else None
+        if plan is not None:
+            out["mask_id_seq"] = plan["mask_ids"]
+            if plan["effective"]:
+                dec_in = self._mlm_mask_fwd(xg, plan)
         # (heads-only training -- the finetune1 stage: nothing at or below the context network learns, its backward is never walked)
         dec_fwd = self._conformer_fwd if m.decoder_name == "conformer" else self._decoder_fwd
         xd, dctx = dec_fwd(W, dec_in, save and self._walks_decoder_fwd())
@@ -812,55 +778,150 @@ class SedEngine:
         if m.has_at:
             actx = self._at_fwd(W, frame16, ectx, save)
             out["at_out"] = actx["at_out"]
-        hctx = {}
-        if m.mlm:
-            M = B * Tdec
-            pred = E(B, Tdec, D)
-            hpre = E(M, D, dt=self.act)
-            if self.split:
-                xd16 = xd.view(M, D)
-                act = E(M, D)
-                with ops.split_precision():
-                    xd16 = split3(xd16, M, D)
-                    gemm_nt(xd16, W["mlm_mlp.0.weight"].ws, EPI_GELU32, bias=self.P("mlm_mlp.0.bias"), outH=hpre,
-                            outF=act)
-                    act = split3(act, M, D)
-                    gemm_nt(act, W["mlm_mlp.2.weight"].ws, EPI_F32, bias=self.P("mlm_mlp.2.bias"), outF=pred)
-            else:
-                xd16 = E(M, D, dt=self.act)
-                call("sed_cast_f32_bf16", xd, xd16, M * D, is_f16(xd16))
-                act = E(M, D, dt=self.act)
-                gemm_nt(xd16, W["mlm_mlp.0.weight"].w, EPI_GELU, bias=self.P("mlm_mlp.0.bias"), outH=hpre, outH2=act)
-                gemm_nt(act, W["mlm_mlp.2.weight"].w, EPI_F32, bias=self.P("mlm_mlp.2.bias"), outF=pred)
-            out["mlm_pred"] = pred
-            hctx = dict(xd16=xd16, hpre=hpre, act=act)
-        else:
-            C = m.class_num
-            if C > NCLS_MAX or (save and C != 10):
-                # any class count (AudioSet-Strong's 407): logits on the fp32 matrix instruction + the transposing sigmoid / pooling kernel
-                # (dasm.wide_head_fwd); the dedicated kernels below serve the 10-class DESED head
-                from .dasm import wide_head_fwd
-                strong, weak, hctx = wide_head_fwd(xd.view(B * Tdec, D), self.P("classifier.weight").detach(), self.P("classifier.bias").detach(),
-                                                   temp_w, pad_mask, B, Tdec, save)
-                hctx = hctx or {}
-            else:
-                strong = E(B, C, Tdec)
-                weak = E(B, C)
-                sums = E(B, C, 2)
-                pm = None
-                if pad_mask is not None:
-                    pm = h2d(pad_mask, torch.uint8, dev)      # (pinned staging: a pageable .to(device) here blocks the host until the whole forward has run)
-                call("sed_head_fwd", xd, self.P("classifier.weight"), self.P("classifier.bias"), float(temp_w), pm, strong,
-                     weak, sums, B, Tdec, C)
-                hctx = dict(strong=strong, sums=sums, temp=float(temp_w))
-            out["strong"], out["weak"] = strong, weak
+        hctx = self._heads_fwd(W, xd, ectx, opt, save, out)
         ctx = None
         if save:
             ctx = dict(B=B, T=T, tp=tp, Tdec=Tdec, ectx=ectx, dctx=dctx, actx=actx, hctx=hctx, xd=xd, W=W,
-                       mlm_plan=mlm_plan if (m.mlm and mlm_plan is not None and mlm_plan["effective"]) else None,
-                       pooled=pooled, lease=lease, wctx=wctx)
+                       mlm_plan=plan if (plan is not None and plan["effective"]) else None, pooled=pooled, lease=lease, **tctx)
         self._lease_ok = False
         return out, ctx
+
+    def _check_forward(self, T, opt, save):
+        """What this engine refuses, before anything is launched.  (Checked on the host: the kernels index the mel rows and the
+        frequency table with the values of `rows`.)"""
+        rows = opt["rows"]
+        if rows is None:
+            return
+        F = len(rows[0])
+        n_sets = 1 + (len(window_starts(T, *opt["win"]["param"])) if opt["win"] else 0)
+        if len(rows) != n_sets or not 1 <= F <= 12 or any(
+                len(r) != F or min(r) < 0 or max(r) >= 12 or any(a >= b for a, b in zip(r, r[1:])) for r in rows):
+            raise ValueError(f"rows: expected {n_sets} sets of equally many strictly increasing frequency rows in [0, 12), got {rows!r}")
+
+    def _trunk_fwd(self, W, mel, pooled, tp, Tdec, opt, save):
+        """Trunk stage: pooled encoder features [B, tp, D] -> the frame sequence the context network reads (`frame_before_mask`) and
+        what `_trunk_bwd` needs of it (merged into the saved context).  Here: interpolation to 1000 frames, then the sliding windows."""
+        assert Tdec == 1000, "MAT-SED expects 1000 decoder frames (passt_sed.py:260)"
+        B = mel.shape[0]
+        xg = torch.empty(B, Tdec, D, dtype=F32, device=mel.device)
+        call("sed_interp_fwd", pooled, xg, B, tp, 1, self.m.decode_ratio)
+        return xg, dict(wctx=self._window_features(W, mel, xg, Tdec, opt, save) if opt["win"] else None)
+
+    def _window_features(self, W, mel, xg, Tdec, opt, save):
+        """Sliding windows (encoder_slide_window.py): the encoder on every window, the windows' features mixed into the 768-wide global
+        sequence `xg` [B, Tdec, D] in place.  Returns what the backward needs (None unless `save`)."""
+        dev = mel.device
+        B, _, T = mel.shape
+        win, step = opt["win"]["param"]
+        toffsets, rows_dev = opt["win"]["toffsets"], opt["rows_dev"]
+        starts = window_starts(T, win, step)
+        if toffsets is None:
+            toffsets = [0] * len(starts)
+        # group the windows by their number of time patches (the last slab of a sweep can be shorter:
+        # min(left + win, T) - left frames, encoder_slide_window.py:28) and fold each group into the batch
+        groups = {}
+        for wi, left in enumerate(starts):
+            width = min(left + win, T) - left
+            groups.setdefault((width - 16) // 10 + 1, []).append(wi)
+        lefts, tps, offs, chunks, row = [0] * len(starts), [0] * len(starts), [0] * len(starts), [], 0
+        wgroups = []
+        for tpw, wis in groups.items():
+            pw, _, gctx = self._encoder_fwd(W, mel, [starts[w] for w in wis], tpw, [toffsets[w] for w in wis], save, want_frame=False,
+                                            rows=None if rows_dev is None else [rows_dev[1 + w] for w in wis], F=opt["F"])
+            chunks.append(pw.view(-1, D))
+            wgroups.append(dict(ectx=gctx, row0=row, rows=len(wis) * B * tpw))
+            for k, w in enumerate(wis):
+                lefts[w], tps[w], offs[w] = round(starts[w] * (Tdec / T)), tpw, row + k * B * tpw
+            row += len(wis) * B * tpw
+        packed = chunks[0] if len(chunks) == 1 else torch.cat(chunks, 0)
+        wdesc = h2d([lefts, tps, offs], torch.int32, dev)       # one upload for the three window tables
+        wl, wt, wo = wdesc[0], wdesc[1], wdesc[2]
+        call("sed_window_mix", packed, wl, wt, wo, len(starts), xg, opt["win"]["mix"], B, Tdec, self.m.decode_ratio)
+        if not save:
+            return None
+        return dict(groups=wgroups, lefts=wl, tps=wt, offs=wo, n=len(starts), mix=opt["win"]["mix"], rows=row)
+
+    _mlm_c = False      # MLM masking on the any-width `_c` kernels (which take the width) instead of the 768-only ones
+
+    def _mlm_mask_fwd(self, xg, plan):
+        """The MLM plan applied to the frame sequence (mask token / random frame / kept), at the sequence's own width."""
+        B, Tdec, Dm = xg.shape
+        dec_in = torch.empty_like(xg)
+        call("sed_mlm_apply_c" if self._mlm_c else "sed_mlm_apply", xg, self.P("mask_token").reshape(Dm), plan["action"], plan["src_idx"],
+             dec_in, B * Tdec, *((Dm,) if self._mlm_c else ()))
+        return dec_in
+
+    def _mlm_mask_bwd(self, g, plan, G):
+        B, Tdec, Dm = g.shape
+        gx = torch.zeros_like(g)
+        dtok = G("mask_token") if G("mask_token") is not None else torch.zeros(Dm, dtype=F32, device=g.device)
+        call("sed_mlm_apply_bwd_c" if self._mlm_c else "sed_mlm_apply_bwd", g, plan["action"], plan["src_idx"], gx, dtok, B * Tdec,
+             *((Dm,) if self._mlm_c else ()))
+        return gx
+
+    def _mlm_head_fwd(self, W, xd, hpre_dt):
+        """mlm_mlp on the context network's output, at its width.  -> (prediction [B, Tdec, out], saved operands); `hpre_dt`: type of
+        the saved GELU pre-activation."""
+        B, Tdec, Dm = xd.shape
+        M = B * Tdec
+        n_out = W["mlm_mlp.2.weight"].w.shape[0]
+        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=xd.device)
+        hpre = E(M, Dm, dt=hpre_dt)
+        if self.split:
+            act = E(M, Dm)
+            pred = E(B, Tdec, n_out)
+            with ops.split_precision():
+                xd16 = split3(xd.view(M, Dm), M, Dm)
+                gemm_nt(xd16, W["mlm_mlp.0.weight"].ws, EPI_GELU32, bias=self.P("mlm_mlp.0.bias"), outH=hpre, outF=act)
+                act = split3(act, M, Dm)      # split images: the first third is the weight-gradient operand
+                gemm_nt(act, W["mlm_mlp.2.weight"].ws, EPI_F32, bias=self.P("mlm_mlp.2.bias"), outF=pred.view(M, n_out))
+        else:
+            pred = E(B, Tdec, n_out)
+            xd16 = E(M, Dm, dt=self.act)
+            call("sed_cast_f32_bf16", xd, xd16, M * Dm, is_f16(xd16))
+            act = E(M, Dm, dt=self.act)
+            gemm_nt(xd16, W["mlm_mlp.0.weight"].w, EPI_GELU, bias=self.P("mlm_mlp.0.bias"), outH=hpre, outH2=act)
+            gemm_nt(act, W["mlm_mlp.2.weight"].w, EPI_F32, bias=self.P("mlm_mlp.2.bias"), outF=pred.view(M, n_out))
+        return pred, dict(xd16=xd16, hpre=hpre, act=act)
+
+    def _mlm_head_bwd(self, W, ctx, dpred, G):
+        B, Tdec, Dm = ctx["xd"].shape
+        if dpred is None:
+            return torch.zeros(B, Tdec, Dm, dtype=F32, device=ctx["xd"].device)
+        hc = ctx["hctx"]
+        M = B * Tdec
+        return self._mlp_bwd(W, "mlm_mlp.0", "mlm_mlp.2", dpred.contiguous().float().view(M, -1), hc["xd16"], hc["hpre"], hc["act"], M,
+                             G, residual=None).view(B, Tdec, Dm)
+
+    def _heads_fwd(self, W, xd, ectx, opt, save, out):
+        """Heads stage: fills `out` from the context network's output xd [B, Tdec, width] (MLM head, or the classifier with its sigmoid
+        and linear-softmax pooling) and returns what `_heads_bwd` reads."""
+        m = self.m
+        B, Tdec, Dm = xd.shape
+        if m.mlm:
+            out["mlm_pred"], hctx = self._mlm_head_fwd(W, xd, self.act)
+        elif self._wide_head(save):
+            # any class count (AudioSet-Strong's 407): logits on the fp32 matrix instruction + the transposing sigmoid / pooling kernel
+            # (dasm.wide_head_fwd); the dedicated kernels serve the 10-class DESED head
+            from .dasm import wide_head_fwd
+            out["strong"], out["weak"], hctx = wide_head_fwd(xd.view(B * Tdec, Dm), self.P("classifier.weight").detach(),
+                                                             self.P("classifier.bias").detach(), opt["temp_w"], opt["pad_mask"], B, Tdec, save)
+        else:
+            # (pinned staging of the mask: a pageable .to(device) here blocks the host until the whole forward has run)
+            pm = None if opt["pad_mask"] is None else h2d(opt["pad_mask"], torch.uint8, xd.device)
+            out["strong"], out["weak"], hctx = self._head10_fwd(xd, float(opt["temp_w"]), pm)
+        return hctx or {}
+
+    def _wide_head(self, save):
+        C = self.m.class_num
+        return C > NCLS_MAX or (save and C != 10)
+
+    def _head10_fwd(self, xd, temp, pm):
+        B, Tdec, C = xd.shape[0], xd.shape[1], self.m.class_num
+        E = lambda *s: torch.empty(*s, dtype=F32, device=xd.device)
+        strong, weak, sums = E(B, C, Tdec), E(B, C), E(B, C, 2)
+        call("sed_head_fwd", xd, self.P("classifier.weight"), self.P("classifier.bias"), temp, pm, strong, weak, sums, B, Tdec, C)
+        return strong, weak, dict(strong=strong, sums=sums, temp=temp)
 
     # ------------------------------------------------------------------ AT head
     def _at_fwd(self, W, frame16, ectx, save):
@@ -912,68 +973,70 @@ class SedEngine:
         """grads: dict of upstream gradients (strong / weak / at_out / mlm_pred / frame_before_mask, any may be None).
         garena: callable name -> fp32 gradient view (zero-initialised) or None when the parameter is frozen."""
         m = self.m
-        W = ctx["W"]
-        B, Tdec = ctx["B"], ctx["Tdec"]
-        dev = ctx["xd"].device
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        Z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
-        G = garena
-        M = B * Tdec
-        Mpad = pad64(M)
-        # ---------------- heads -> d(decoder output)
-        if m.mlm:
-            dpred = grads.get("mlm_pred")
-            hc = ctx["hctx"]
-            if dpred is None:
-                g = Z(B, Tdec, D)
-            else:
-                dpred = dpred.contiguous().float()
-                g = self._mlp_bwd(W, "mlm_mlp.0", "mlm_mlp.2", dpred.view(M, D), hc["xd16"], hc["hpre"], hc["act"], M,
-                                  G, residual=None)
-        else:
-            hc = ctx["hctx"]
-            ds, dw = grads.get("strong"), grads.get("weak")
-            g = E(B, Tdec, D)
-            if ds is None and dw is None:
-                g.zero_()
-            elif hc.get("wide"):
-                from .dasm import wide_head_bwd
-                g = wide_head_bwd(hc, self.P("classifier.weight").detach(), ds, dw, G("classifier.weight"), G("classifier.bias")).view(B, Tdec, D)
-            else:
-                ds = None if ds is None else ds.contiguous().float()
-                dw = None if dw is None else dw.contiguous().float()
-                call("sed_head_bwd", ctx["xd"], self.P("classifier.weight"), hc["strong"], hc["sums"], ds, dw, hc["temp"],
-                     g, G("classifier.weight"), G("classifier.bias"), B, Tdec, m.class_num)
+        W, G = ctx["W"], garena
+        ectx = ctx["ectx"]
+        depth = len(ectx["layers"])
+        at_grad = grads["at_out"].contiguous().float() if (m.has_at and grads.get("at_out") is not None) else None
+        # ---------------- heads -> d(context-network output) [B, Tdec, width] (and d(final-norm frame tokens) of a head that reads them)
+        g, dframe = self._heads_bwd(W, ctx, grads, G)
         # ---------------- nothing at or below the context network learns (finetune1: heads only): neither it nor the encoder is walked
-        if not self._walks_decoder(G, len(ctx["ectx"]["layers"])) and grads.get("frame_before_mask") is None:
+        if not self._walks_decoder(G, depth) and grads.get("frame_before_mask") is None:
             if hook is not None:
                 hook("decoder")
-            if m.has_at and grads.get("at_out") is not None:
-                self._at_bwd(W, ctx["actx"], ctx["ectx"], grads["at_out"].contiguous().float(), G, need_dx=False)
+            if at_grad is not None:
+                self._at_bwd(W, ctx["actx"], ectx, at_grad, G, need_dx=False)
             if hook is not None:
                 hook("heads")
             return
-        # ---------------- context network
-        if m.decoder_name == "conformer":
-            g = self._conformer_bwd(W, ctx["dctx"], g, G, G("decoder.blocks.0.self_attn.in_proj.weight") is not None)
-        else:
-            dec_trainable = G("decoder.encoder_blocks.0.attn.in_proj.weight") is not None
-            g = self._decoder_bwd(W, ctx["dctx"], g, G, dec_trainable)
-        # g = d(decoder input) [B, Tdec, D]
+        g = self._context_bwd(W, ctx, g, G)        # d(context-network input)
         if ctx["mlm_plan"] is not None:
-            plan = ctx["mlm_plan"]
-            gx = Z(B, Tdec, D)
-            dtok = G("mask_token")
-            call("sed_mlm_apply_bwd", g, plan["action"], plan["src_idx"], gx, dtok if dtok is not None else Z(D), M)
-            g = gx
+            g = self._mlm_mask_bwd(g, ctx["mlm_plan"], G)
         if hook is not None:
             hook("decoder")  # classifier / mlm head / context-network / mask_token gradients are final
         dfbm = grads.get("frame_before_mask")
         if dfbm is not None:
             g = g + dfbm.contiguous().float()
-        # ---------------- sliding windows (student with encoder_win=True): x = (1 - mix) global + mix * local
-        ectx = ctx["ectx"]
-        tp = ctx["tp"]
+        dpooled = self._trunk_bwd(W, ctx, g, G)
+        # ---------------- what arrives at the top of the encoder stack (AT head, a head's frame tokens), then f_pool and the stack
+        lo, _ = self._lowest_trainable(G, depth)
+        genc = None
+        if at_grad is not None:
+            genc = self._at_bwd(W, ctx["actx"], ectx, at_grad, G, need_dx=lo < depth)
+        if dframe is not None:
+            genc = self._frame_norm_bwd(ectx, dframe, G, need_dx=lo < depth)
+        self._encoder_bwd(W, ectx, genc, dpooled, G, hook)
+
+    def _heads_bwd(self, W, ctx, grads, G):
+        """-> (gradient of the context network's output [B, Tdec, width], gradient of the final-norm patch tokens or None)."""
+        if self.m.mlm:
+            return self._mlm_head_bwd(W, ctx, grads.get("mlm_pred"), G), None
+        hc = ctx["hctx"]
+        ds, dw = grads.get("strong"), grads.get("weak")
+        if ds is None and dw is None:
+            return torch.zeros_like(ctx["xd"]), None
+        if hc.get("wide"):
+            from .dasm import wide_head_bwd
+            g = wide_head_bwd(hc, self.P("classifier.weight").detach(), ds, dw, G("classifier.weight"), G("classifier.bias"))
+            return g.view(ctx["xd"].shape), None
+        return self._head10_bwd(ctx, None if ds is None else ds.contiguous().float(), None if dw is None else dw.contiguous().float(), G), None
+
+    def _head10_bwd(self, ctx, ds, dw, G):
+        hc, g = ctx["hctx"], torch.empty_like(ctx["xd"])
+        call("sed_head_bwd", ctx["xd"], self.P("classifier.weight"), hc["strong"], hc["sums"], ds, dw, hc["temp"],
+             g, G("classifier.weight"), G("classifier.bias"), ctx["B"], ctx["Tdec"], self.m.class_num)
+        return g
+
+    def _context_bwd(self, W, ctx, g, G):
+        if self.m.decoder_name == "conformer":
+            return self._conformer_bwd(W, ctx["dctx"], g, G, G("decoder.blocks.0.self_attn.in_proj.weight") is not None)
+        return self._decoder_bwd(W, ctx["dctx"], g, G, G("decoder.encoder_blocks.0.attn.in_proj.weight") is not None)
+
+    def _trunk_bwd(self, W, ctx, g, G):
+        """Backward of `_trunk_fwd`: d(frame_before_mask) -> d(pooled) [B, tp, D].  Here the sliding windows (student with
+        encoder_win=True: x = (1 - mix) global + mix * local), each group's encoder pass without stage hooks, then the interpolation."""
+        m = self.m
+        B, Tdec, tp = ctx["B"], ctx["Tdec"], ctx["tp"]
+        E = lambda *s: torch.empty(*s, dtype=F32, device=g.device)
         wctx = ctx.get("wctx")
         if wctx is not None:
             dpacked = E(wctx["rows"], D)
@@ -981,17 +1044,12 @@ class SedEngine:
             call("sed_window_mix_bwd", g.contiguous(), wctx["lefts"], wctx["tps"], wctx["offs"], wctx["n"], dpacked, gglob,
                  wctx["mix"], B, Tdec, m.decode_ratio, wctx["rows"])
             g = gglob
-            for grp in wctx["groups"]:       # every window group: f_pool -> blocks -> patch embedding, no stage hooks yet
+            for grp in wctx["groups"]:
                 gctx = grp["ectx"]
                 self._encoder_bwd(W, gctx, None, dpacked[grp["row0"]:grp["row0"] + grp["rows"]].view(gctx["B"], gctx["tp"], D), G, None)
-        # ---------------- interp + f_pool -> encoder layer `feature_layer`
         dpooled = E(B, tp, D)
         call("sed_interp_bwd", g, dpooled, B, tp, 1, m.decode_ratio)
-        lo, embed_train = self._lowest_trainable(G, len(ectx["layers"]))
-        genc = None  # gradient of the encoder residual stream, built from the top
-        if m.has_at and grads.get("at_out") is not None:
-            genc = self._at_bwd(W, ctx["actx"], ectx, grads["at_out"].contiguous().float(), G, need_dx=lo < len(ectx["layers"]))
-        self._encoder_bwd(W, ectx, genc, dpooled, G, hook)
+        return dpooled
 
     _BELOW_HEADS = ("decoder.", "out_norm.", "mask_token", "f_pool_module.")
 
@@ -1032,71 +1090,93 @@ class SedEngine:
         return depth
 
     def _lowest_trainable(self, G, depth):
-        """Index of the lowest encoder block with a trainable tensor (`depth` if none; 0 when the patch embedding / position tables train:
-        recipes/desed/finetune/passt/setting.py:44-60 freezes everything below `freeze_layer` except the final norm)."""
+        """(index of the lowest encoder block a backward has to reach -- `depth` if none --, does the patch embedding train): decided
+        once per backward (`_scan_lowest_trainable`), then read by every stage that asks."""
         key = (id(G), depth)
         hit = getattr(self, "_lo_cache", None)
         if hit is not None and hit[0] == key:
             return hit[1]
+        res = self._scan_lowest_trainable(G, depth)
+        self._lo_cache = (key, res, G)      # (G kept alive so that its id cannot be recycled while cached)
+        return res
+
+    def _scan_lowest_trainable(self, G, depth):
+        """From the gradient views: the lowest block with a trainable tensor; 0 when the patch embedding / position tables train
+        (recipes/desed/finetune/passt/setting.py:44-60 freezes everything below `freeze_layer` except the final norm)."""
         embed = ("backbone.patch_embed.proj.weight", "backbone.patch_embed.proj.bias", "backbone.cls_token", "backbone.dist_token",
                  "backbone.new_pos_embed", "backbone.freq_new_pos_embed", "backbone.time_new_pos_embed")
         block = ("norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias", "norm2.weight",
                  "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")
-        res = (depth, False)
         if any(G(n) is not None for n in embed):           # ANY tensor of a stage makes the stage (and everything above it) run
-            res = (0, True)
-        else:
-            for i in range(depth):
-                if any(G(f"backbone.blocks.{i}.{t}") is not None for t in block):
-                    res = (i, False)
-                    break
-        self._lo_cache = (key, res, G)      # (G kept alive so that its id cannot be recycled while cached)
-        return res
+            return 0, True
+        for i in range(depth):
+            if any(G(f"backbone.blocks.{i}.{t}") is not None for t in block):
+                return i, False
+        return depth, False
+
+    def _fpool_bwd(self, W, ectx, dpooled, G, need_dx):
+        """Backward of `_fpool_fwd`; -> its gradient at the encoder residual stream of the tapped layer [B, N, D] (cls / dist rows
+        zero), or None when `need_dx` is false and the form can skip it."""
+        B, N, tp, F = ectx["B"], ectx["N"], ectx["tp"], ectx["F"]
+        dev = dpooled.device
+        Z = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
+        gpool = Z(B, N, D) if need_dx else None
+        dtok_tmp = torch.empty(B, N, D, dtype=F32, device=dev)
+        pool_dx = gpool if need_dx else Z(B, N, D)
+        call("sed_fpool_rows_bwd", dpooled.contiguous(), ectx["pool_x"], ectx["pool_mean"], ectx["pool_rstd"], self.P("out_norm.weight"),
+             dtok_tmp, pool_dx, G("out_norm.weight"), G("out_norm.bias"), B, tp, F)
+        return gpool
+
+    def _frame_norm_bwd(self, ectx, dframe, G, need_dx):
+        """A head that reads the final-norm patch tokens (DASM's tagging stream, detect_any_sound.py:350): their gradient [B, N - 2, D]
+        through backbone.norm into the top of the stack, like the AT head's."""
+        B, N = ectx["B"], ectx["N"]
+        dfull = torch.zeros(B, N, D, dtype=F32, device=dframe.device)
+        dfull[:, 2:, :] = dframe
+        genc = torch.empty(B, N, D, dtype=F32, device=dframe.device)
+        call("sed_layernorm_bwd", dfull.view(B * N, D), ectx["x_final"], ectx["fmean"], ectx["frstd"], self.P("backbone.norm.weight"), 1.0,
+             genc.view(B * N, D), 0, G("backbone.norm.weight"), G("backbone.norm.bias"), B * N, D)
+        return genc if need_dx else None
+
+    _embed_stage_always = False     # fire the "embed" stage hook after every walk of the stack, whether or not the embedding trains
 
     def _encoder_bwd(self, W, ectx, genc, dpooled, G, hook):
         """Backward of one encoder pass (the global one, or a group of sliding windows folded into the batch): f_pool at the tapped
         layer, the blocks from the top saved one down to the lowest trainable one, then the patch embedding.  `genc` is the gradient
-        arriving at the top of the stack (AT head) or None; gradients accumulate into the arena views."""
+        arriving at the top of the stack (AT head) or None; gradients accumulate into the arena views.  Overridable pieces:
+        `_fpool_bwd`, `_enc_layer_bwd` (where a block's weight gradients go), `_scan_lowest_trainable`."""
         m = self.m
         B, N, tp, F = ectx["B"], ectx["N"], ectx["tp"], ectx["F"]
         dev = dpooled.device
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        Z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
         depth = len(ectx["layers"])
         lo, embed_train = self._lowest_trainable(G, depth)
         tap = m.passt_feature_layer - 1                      # f_pool reads the output of block `tap`
-        need_pool_dx = lo <= tap
-        gpool = Z(B, N, D) if need_pool_dx else None
-        dtok_tmp = E(B, N, D)
-        pool_dx = gpool if need_pool_dx else Z(B, N, D)
-        call("sed_fpool_rows_bwd", dpooled.contiguous(), ectx["pool_x"], ectx["pool_mean"], ectx["pool_rstd"], self.P("out_norm.weight"),
-             dtok_tmp, pool_dx, G("out_norm.weight"), G("out_norm.bias"), B, tp, F)
+        gpool = self._fpool_bwd(W, ectx, dpooled, G, need_dx=lo <= tap)
         if hook is not None:
             hook("heads")  # AT head, out_norm (and backbone.norm) gradients are final
         if lo >= depth:
             return
         if genc is None:
-            genc = Z(B, N, D)
+            genc = torch.zeros(B, N, D, dtype=F32, device=dev)
         for li in range(depth - 1, lo - 1, -1):
             if li == tap:
                 genc.add_(gpool)
             genc = self._enc_layer_bwd(W, ectx, li, genc, G)
             if hook is not None:
                 hook(("block", li))
-        if not embed_train:
-            return
-        # patch embedding + positional tables (one slab of the batch per window / time offset)
-        nS = ectx["nS"]
-        Bs = B // nS
-        Ms = Bs * F * tp
-        Mp = nS * Ms
-        dconv16 = E(Mp, D, dt=BF16)
-        for sidx in range(nS):
-            call("sed_assemble_tokens_rows_bwd", genc[sidx * Bs:(sidx + 1) * Bs], dconv16[sidx * Ms:(sidx + 1) * Ms],
-                 G("backbone.cls_token"), G("backbone.dist_token"), G("backbone.new_pos_embed"), G("backbone.freq_new_pos_embed"),
-                 G("backbone.time_new_pos_embed"), ectx["rows"][sidx], F, int(ectx["toffsets"][sidx]), Bs, tp)
-        self._dw_accum(dconv16, ectx["cols"], Mp, G("backbone.patch_embed.proj.weight"), G("backbone.patch_embed.proj.bias"))
-        if hook is not None:
+        if embed_train:
+            # patch embedding + positional tables (one slab of the batch per window / time offset)
+            nS = ectx["nS"]
+            Bs = B // nS
+            Ms = Bs * F * tp
+            Mp = nS * Ms
+            dconv16 = torch.empty(Mp, D, dtype=BF16, device=dev)
+            for sidx in range(nS):
+                call("sed_assemble_tokens_rows_bwd", genc[sidx * Bs:(sidx + 1) * Bs], dconv16[sidx * Ms:(sidx + 1) * Ms],
+                     G("backbone.cls_token"), G("backbone.dist_token"), G("backbone.new_pos_embed"), G("backbone.freq_new_pos_embed"),
+                     G("backbone.time_new_pos_embed"), ectx["rows"][sidx], F, int(ectx["toffsets"][sidx]), Bs, tp)
+            self._dw_accum(dconv16, ectx["cols"], Mp, G("backbone.patch_embed.proj.weight"), G("backbone.patch_embed.proj.bias"))
+        if hook is not None and (embed_train or self._embed_stage_always):
             hook("embed")
 
     def _g16_take(self, g):
@@ -1175,7 +1255,6 @@ class SedEngine:
         into `residual` (f32 [M, D]) when given.  Weight/bias grads go to the arena when trainable."""
         dev = dy.device
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        Mpad = pad64(M)
         w1, w2 = W[n1 + ".weight"], W[n2 + ".weight"]
         hid = w1.w.shape[0]
         n_out = w2.w.shape[0]
@@ -1199,7 +1278,6 @@ class SedEngine:
         L = ectx["layers"][li]
         B, N, Npad = ectx["B"], ectx["N"], ectx["Npad"]
         M = B * N
-        Mpad = pad64(M)
         dev = g.device
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         g2 = g.view(M, D)
@@ -1392,7 +1470,6 @@ class SedEngine:
         dev = dat.device
         B, N = ectx["B"], ectx["N"]
         M = B * N
-        Mpad = pad64(M)
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         Z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
         pre = "at_adpater.0."

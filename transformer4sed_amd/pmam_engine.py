@@ -434,71 +434,54 @@ class PmamEngine(SedEngine):
             cur = x2
         return cur, ctx
 
-    # ------------------------------------------------------------------ full forward (passt_cnn.py:31-88)
-    def forward(self, mel, encoder_win=False, mix_rate=0.5, win_param=(512, 49), temp_w=1.0, pad_mask=None, mlm_plan=None,
-                toffsets=None, save=False, drop_masks=None):
+    # ------------------------------------------------------------------ stages of SedEngine.forward (passt_cnn.py:31-88)
+    _mlm_c = True               # the merged sequence is decoder_dim wide
+    _embed_stage_always = True  # (ddp.GradReducer's stage order of these models ends with "embed" whenever the stack is walked)
+
+    def _walks_decoder_fwd(self):
+        return True     # no heads-only shortcut here: the context network is always walked, forward and backward
+
+    def _walks_decoder(self, G, depth):
+        return True
+
+    def _check_forward(self, T, opt, save):
+        assert T == 1000
+        if opt["rows"] is not None:
+            raise NotImplementedError("frequency patchout is not part of the PMAM path")
+        if opt["win"] is not None and save:
+            raise NotImplementedError("gradient through the sliding-window path is not needed by any PMAM config")
+
+    def _project(self, W, name, x, rows):
+        """Linear `name` on fp32 rows in split precision -> fp32 [rows, decoder_dim]."""
+        out = torch.empty(rows, self.m.decoder_dim, dtype=F32, device=x.device)
+        with ops.split_precision():
+            gemm_nt(split3(x, rows, x.shape[1]), W[name + ".weight"].ws, EPI_F32, bias=self.P(name + ".bias"), outF=out)
+        return out
+
+    def _trunk_fwd(self, W, mel, pooled, tp, Tdec, opt, save):
+        """CNN branch, the two projectors, the merge (passt_cnn.py:57-62); DASM: LayerNorm after the merge (detect_any_sound.py:346)."""
         m = self.m
         dev = mel.device
-        if mel.dtype != F32 or not mel.is_contiguous():
-            mel = mel.contiguous().float()
-        B, Fm, T = mel.shape
-        assert Fm == 128 and T == 1000
-        Dd = m.decoder_dim
-        W = self._weights(need_t=save)
-        lease = self._lease(save)
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        out = {}
-        tp = 99
-        dasm = getattr(m, "dasm_head", None)       # DASM (dasm.py): same trunk, LayerNorm after the merge, query decoder + dual-stream head
-        pooled, frame16, ectx = self._encoder_fwd(W, mel, [0], tp, [0], save, want_frame=m.has_at or dasm is not None)
-        Tdec = (tp + 1) * m.decode_ratio
-        feat, cctx = self._cnn_fwd(W, mel, train=m.training, save=save, drop_masks=drop_masks)
+        B, Dd = mel.shape[0], m.decoder_dim
+        E = lambda *s: torch.empty(*s, dtype=F32, device=dev)
+        feat, cctx = self._cnn_fwd(W, mel, train=m.training, save=save, drop_masks=opt["drop_masks"])
         Tc = cctx["Tc"]
-        Cl = feat.shape[1]
-        P2 = E(B * Tc, Dd)
-        with ops.split_precision():
-            gemm_nt(split3(feat, B * Tc, Cl), W["cnn_projector.weight"].ws, EPI_F32, bias=self.P("cnn_projector.bias"), outF=P2)
+        P2 = self._project(W, "cnn_projector", feat, B * Tc)
         assert Tdec % Tc == 0
         xg = E(B, Tdec, Dd)
-        if encoder_win:
+        if opt["win"] is not None:
             # sliding windows (teacher / validation of the PMAM finetune stage): local and global features are mixed at encoder
             # width (passt_cnn.py:41-46), so the projector runs on all Tdec frames
-            if save:
-                raise NotImplementedError("gradient through the sliding-window path is not needed by any PMAM config")
-            from .engine import window_starts
             x768 = E(B, Tdec, D)
             call("sed_interp_fwd", pooled, x768, B, tp, 1, m.decode_ratio)
-            win, step = win_param
-            starts = window_starts(T, win, step)
-            if toffsets is None:
-                toffsets = [0] * len(starts)
-            groups = {}
-            for wi, left in enumerate(starts):
-                groups.setdefault((min(left + win, T) - left - 16) // 10 + 1, []).append(wi)
-            lefts, tps, offs, chunks, row = [0] * len(starts), [0] * len(starts), [0] * len(starts), [], 0
-            for tpw, wis in groups.items():
-                pw, _, _ = self._encoder_fwd(W, mel, [starts[w] for w in wis], tpw, [toffsets[w] for w in wis], False, want_frame=False)
-                chunks.append(pw.view(-1, D))
-                for k, w in enumerate(wis):
-                    lefts[w], tps[w], offs[w] = round(starts[w] * (Tdec / T)), tpw, row + k * B * tpw
-                row += len(wis) * B * tpw
-            packed = chunks[0] if len(chunks) == 1 else torch.cat(chunks, 0)
-            i32 = lambda v: h2d(v, torch.int32, dev)
-            call("sed_window_mix", packed, i32(lefts), i32(tps), i32(offs), len(starts), x768, float(mix_rate), B, Tdec, m.decode_ratio)
-            P1 = E(B * Tdec, Dd)
-            with ops.split_precision():
-                gemm_nt(split3(x768.view(B * Tdec, D), B * Tdec, D), W["transformer_projector.weight"].ws, EPI_F32,
-                        bias=self.P("transformer_projector.bias"), outF=P1)
-            call("sed_pmam_merge", P1, P2, self.P("merge_weight"), xg, B, Tdec, 0, 1, Tc, Tdec // Tc, Dd)
-        else:
-            # transformer_projector / cnn_projector before the interpolations
-            P1 = E(B * tp, Dd)
-            with ops.split_precision():
-                gemm_nt(split3(pooled.view(B * tp, D), B * tp, D), W["transformer_projector.weight"].ws, EPI_F32,
-                        bias=self.P("transformer_projector.bias"), outF=P1)
-            call("sed_pmam_merge", P1, P2, self.P("merge_weight"), xg, B, tp, 1, m.decode_ratio, Tc, Tdec // Tc, Dd)
+            self._window_features(W, mel, x768, Tdec, opt, False)
+            src, rows, pad, up = x768, Tdec, 0, 1
+        else:       # transformer_projector / cnn_projector before the interpolations
+            src, rows, pad, up = pooled, tp, 1, m.decode_ratio
+        P1 = self._project(W, "transformer_projector", src.view(B * rows, D), B * rows)
+        call("sed_pmam_merge", P1, P2, self.P("merge_weight"), xg, B, rows, pad, up, Tc, Tdec // Tc, Dd)
         nam = None
-        if dasm is not None:      # norm_after_merge (detect_any_sound.py:346)
+        if getattr(m, "dasm_head", None) is not None:
             xn = E(B, Tdec, Dd)
             nm_, nr_ = (E(B * Tdec), E(B * Tdec)) if save else (None, None)
             call("sed_layernorm_fwd", xg.view(B * Tdec, Dd), self.P("norm_after_merge.weight"), self.P("norm_after_merge.bias"), 1e-5, 1.0,
@@ -506,69 +489,45 @@ class PmamEngine(SedEngine):
             if save:
                 nam = dict(x=xg, mean=nm_, rstd=nr_)
             xg = xn
-        out["frame_before_mask"] = xg
-        dec_in = xg
-        plan = mlm_plan if (m.mlm and mlm_plan is not None) else None
-        if plan is not None:
-            out["mask_id_seq"] = plan["mask_ids"]
-            if plan["effective"]:
-                dec_in = E(B, Tdec, Dd)
-                call("sed_mlm_apply_c", xg, self.P("mask_token").reshape(Dd), plan["action"], plan["src_idx"], dec_in, B * Tdec, Dd)
-        xd, dctx = self._decoder_fwd(W, dec_in, save)
-        actx = None
-        if m.has_at:
-            actx = self._at_fwd(W, frame16, ectx, save)
-            out["at_out"] = actx["at_out"]
-        M = B * Tdec
+        return xg, dict(cctx=cctx, feat=feat, P1=P1, P2=P2, nam=nam)
+
+    def _heads_fwd(self, W, xd, ectx, opt, save, out):
+        m = self.m
+        dasm = getattr(m, "dasm_head", None)       # DASM (dasm.py): same trunk, query decoder + dual-stream head
         if dasm is not None:
             # frame tokens of the final norm without the cls / dist tokens (detect_any_sound.py:364), fp32 (engine._encoder_fwd wrote them
             # beside the 16-bit image); the SED decoder's output goes to sed_head inside the head
-            N = 2 + 12 * tp
-            ft = self._frame32.view(B, N, D)[:, 2:, :].contiguous()
+            ft = self._frame32.view(xd.shape[0], ectx["N"], D)[:, 2:, :].contiguous()
             m._last_x_dec = xd            # (kept for tests / inspection: the SED decoder's output that sed_head reads)
             dc = m.__dict__["_dasm_call"]
-            hd = dasm.forward(ft, xd, query=dc["query"], tgt_mask=dc["tgt_mask"], temp_w=float(temp_w), pad_mask=pad_mask,
+            hd = dasm.forward(ft, xd, query=dc["query"], tgt_mask=dc["tgt_mask"], temp_w=float(opt["temp_w"]), pad_mask=opt["pad_mask"],
                               query_type=dc["query_type"], save=save, train=bool(m.training), drop_seed=m._next_drop_seed() if m.training else 0)
             out["strong"], out["weak"], out["at_out"] = hd[0], hd[1], hd[2]
             hctx = hd[4] if save else None
             if save:
                 hctx["query_grads"] = list(getattr(m, "_dasm_query_grads", ()) or ()) or None
-        elif m.mlm:
-            hpre = E(M, Dd, dt=BF16 if save else self.act)
-            act = E(M, Dd)
-            xds = split3(xd.view(M, Dd), M, Dd)
-            with ops.split_precision():
-                gemm_nt(xds, W["mlm_mlp.0.weight"].ws, EPI_GELU32, bias=self.P("mlm_mlp.0.bias"), outH=hpre, outF=act)
-            pred = E(B, Tdec, m.mlm_out)
-            acts = split3(act, M, Dd)
-            with ops.split_precision():
-                gemm_nt(acts, W["mlm_mlp.2.weight"].ws, EPI_F32, bias=self.P("mlm_mlp.2.bias"), outF=pred.view(M, m.mlm_out))
-            out["mlm_pred"] = pred
-            hctx = dict(xd=xds, hpre=hpre, act=acts)       # split images: first third = weight-gradient operand
-        else:
-            # classifier + sigmoid + linear-softmax pooling (passt_cnn.py:74-86) on the 768-wide head kernel: decoder output and
-            # classifier weight zero-padded from Dd to 768 columns (the dot products are unchanged)
-            C = m.class_num
-            if C != 10:      # any class count (the 407 AudioSet-Strong classes): GEMM head, dasm.wide_head_fwd
-                from .dasm import wide_head_fwd
-                strong, weak, hctx = wide_head_fwd(xd.view(M, Dd), self.P("classifier.weight").detach(), self.P("classifier.bias").detach(), temp_w,
-                                                   pad_mask, B, Tdec, save)
-            else:
-                xd_pad = torch.zeros(B, Tdec, D, dtype=F32, device=dev)
-                xd_pad[:, :, :Dd] = xd
-                w_pad = torch.zeros(C, D, dtype=F32, device=dev)
-                w_pad[:, :Dd] = self.P("classifier.weight").detach()
-                strong, weak, sums = E(B, C, Tdec), E(B, C), E(B, C, 2)
-                pm = None if pad_mask is None else h2d(pad_mask, torch.uint8, dev)
-                call("sed_head_fwd", xd_pad, w_pad, self.P("classifier.bias"), float(temp_w), pm, strong, weak, sums, B, Tdec, C)
-                hctx = dict(strong=strong, sums=sums, temp=float(temp_w), xd_pad=xd_pad, w_pad=w_pad)
-            out["strong"], out["weak"] = strong, weak
-        ctx = None
-        if save:
-            ctx = dict(B=B, T=T, tp=tp, Tdec=Tdec, ectx=ectx, dctx=dctx, actx=actx, cctx=cctx, xd=xd, W=W, pooled=pooled, feat=feat, P1=P1,
-                       P2=P2, hctx=hctx, mlm_plan=plan if (plan is not None and plan["effective"]) else None, lease=lease, nam=nam)
-        self._lease_ok = False
-        return out, ctx
+            return hctx
+        if m.mlm:
+            out["mlm_pred"], hctx = self._mlm_head_fwd(W, xd, BF16 if save else self.act)
+            return hctx
+        return super()._heads_fwd(W, xd, ectx, opt, save, out)      # classifier + sigmoid + linear-softmax pooling (passt_cnn.py:74-86)
+
+    def _wide_head(self, save):
+        return self.m.class_num != 10      # any class count (the 407 AudioSet-Strong classes): GEMM head, dasm.wide_head_fwd
+
+    def _head10_fwd(self, xd, temp, pm):
+        """The 768-wide head kernel on the decoder output and the classifier weight zero-padded from decoder_dim to 768 columns (the dot
+        products are unchanged)."""
+        B, Tdec, Dd = xd.shape
+        C, dev = self.m.class_num, xd.device
+        E = lambda *s: torch.empty(*s, dtype=F32, device=dev)
+        xd_pad = torch.zeros(B, Tdec, D, dtype=F32, device=dev)
+        xd_pad[:, :, :Dd] = xd
+        w_pad = torch.zeros(C, D, dtype=F32, device=dev)
+        w_pad[:, :Dd] = self.P("classifier.weight").detach()
+        strong, weak, sums = E(B, C, Tdec), E(B, C), E(B, C, 2)
+        call("sed_head_fwd", xd_pad, w_pad, self.P("classifier.bias"), temp, pm, strong, weak, sums, B, Tdec, C)
+        return strong, weak, dict(strong=strong, sums=sums, temp=temp, xd_pad=xd_pad, w_pad=w_pad)
 
     # ==================================================================== backward
     def _dw_accum(self, dy, x, M, gW, bias=None, dy16=None, k_in=None):
@@ -810,10 +769,11 @@ class PmamEngine(SedEngine):
             dctx["layers"][li] = None
         return g
 
-    def _fpool_bwd(self, W, ectx, dpooled, B, tp, G):
-        """-> gradient of the encoder residual stream at the feature layer [B, N, D] (cls / dist rows zero)."""
+    def _fpool_bwd(self, W, ectx, dpooled, G, need_dx):
+        if self.m.f_pool_name != "attention":
+            return super()._fpool_bwd(W, ectx, dpooled, G, need_dx)
         dev = dpooled.device
-        N = ectx["N"]
+        B, N, tp = ectx["B"], ectx["N"], ectx["tp"]
         M = B * N
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         Z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
@@ -840,76 +800,59 @@ class PmamEngine(SedEngine):
              gpool.view(M, D), 0, G("out_norm.weight"), G("out_norm.bias"), M, D)
         return gpool
 
-    def _backward_impl(self, ctx, grads, garena, hook=None):
+    # ------------------------------------------------------------------ stages of SedEngine._backward_impl
+    def _heads_bwd(self, W, ctx, grads, G):
         m = self.m
-        W = ctx["W"]
-        B, Tdec, tp = ctx["B"], ctx["Tdec"], ctx["tp"]
-        Dd = m.decoder_dim
-        dev = ctx["xd"].device
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        Z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
-        G = garena
-        M = B * Tdec
-        hc = ctx["hctx"]
+        m._at_grad_seen = m.has_at and grads.get("at_out") is not None
         dasm = getattr(m, "dasm_head", None)
-        dframe = None
-        if dasm is not None:
-            # query decoder + dual-stream head (dasm.py): gradients of the SED decoder's output and of the backbone's frame tokens
-            lowest_fwd = self._lowest_trainable_fwd(m.depth)
-            norm_train = G("backbone.norm.weight") is not None
-            dframe, g = dasm.backward(hc, grads.get("strong"), grads.get("weak"), grads.get("at_out"), G,
-                                      need_dframe=lowest_fwd < m.depth or norm_train)
-            m._extra_input_grads = [d for d, want in zip(hc.get("dquery") or [], hc.get("query_grads") or []) if want]
-        elif m.mlm:
-            dpred = grads.get("mlm_pred")
-            if dpred is None:
-                g = Z(B, Tdec, Dd)
-            else:
-                g = self._mlp_bwd(W, "mlm_mlp.0", "mlm_mlp.2", dpred.contiguous().float().view(M, m.mlm_out), hc["xd"],
-                                  hc["hpre"], hc["act"], M, G, residual=None).view(B, Tdec, Dd)
-        else:
-            ds, dw = grads.get("strong"), grads.get("weak")
-            if ds is None and dw is None:
-                g = Z(B, Tdec, Dd)
-            elif hc.get("wide"):
-                from .dasm import wide_head_bwd
-                g = wide_head_bwd(hc, self.P("classifier.weight").detach(), ds, dw, G("classifier.weight"), G("classifier.bias")).view(B, Tdec, Dd)
-            else:
-                ds = None if ds is None else ds.contiguous().float()
-                dw = None if dw is None else dw.contiguous().float()
-                g_pad = E(B, Tdec, D)
-                gw_pad = Z(m.class_num, D)
-                call("sed_head_bwd", hc["xd_pad"], hc["w_pad"], hc["strong"], hc["sums"], ds, dw, hc["temp"], g_pad, gw_pad,
-                     G("classifier.bias") if G("classifier.bias") is not None else Z(m.class_num), B, Tdec, m.class_num)
-                if G("classifier.weight") is not None:
-                    G("classifier.weight").add_(gw_pad[:, :Dd])
-                g = g_pad[:, :, :Dd].contiguous()
+        if dasm is None:
+            return super()._heads_bwd(W, ctx, grads, G)
+        # query decoder + dual-stream head (dasm.py): gradients of the SED decoder's output and of the backbone's frame tokens
+        hc = ctx["hctx"]
+        need_dframe = self._lowest_trainable_fwd(m.depth) < m.depth or G("backbone.norm.weight") is not None
+        dframe, g = dasm.backward(hc, grads.get("strong"), grads.get("weak"), grads.get("at_out"), G, need_dframe=need_dframe)
+        m._extra_input_grads = [d for d, want in zip(hc.get("dquery") or [], hc.get("query_grads") or []) if want]
+        return g, dframe
+
+    def _head10_bwd(self, ctx, ds, dw, G):
+        m, hc = self.m, ctx["hctx"]
+        B, Tdec, Dd = ctx["xd"].shape
+        Z = lambda *s: torch.zeros(*s, dtype=F32, device=ctx["xd"].device)
+        g_pad = torch.empty(B, Tdec, D, dtype=F32, device=ctx["xd"].device)
+        gw_pad = Z(m.class_num, D)
+        call("sed_head_bwd", hc["xd_pad"], hc["w_pad"], hc["strong"], hc["sums"], ds, dw, hc["temp"], g_pad, gw_pad,
+             G("classifier.bias") if G("classifier.bias") is not None else Z(m.class_num), B, Tdec, m.class_num)
+        if G("classifier.weight") is not None:
+            G("classifier.weight").add_(gw_pad[:, :Dd])
+        return g_pad[:, :, :Dd].contiguous()
+
+    def _context_bwd(self, W, ctx, g, G):
+        """The context network's backward into the gradient-image slots of this backward (`_grad_slots`: the CNN branch's are filled by
+        `_trunk_bwd`), then the scatter that returns the context network's to the masters."""
         dec_train = G("decoder.encoder_blocks.0.attn.in_proj.weight") is not None
         cnn_train = G("cnn.cnn.conv0.weight") is not None
-        slots, scatter = self._grad_slots(B, dev, G, dec_train, cnn_train)
+        slots, scatter = ctx["gslots"] = self._grad_slots(ctx["B"], g.device, G, dec_train, cnn_train)
         g = self._decoder_bwd(W, ctx["dctx"], g, G, dec_train, slots)
         if dec_train:
             self._join_dw()      # out_proj / in_proj gradient images were filled on the weight-gradient side stream
             if "dec" in scatter:
                 call("sed_scatter_add_f32", *scatter["dec"])
-        if ctx["mlm_plan"] is not None:
-            plan = ctx["mlm_plan"]
-            gx = Z(B, Tdec, Dd)
-            dtok = G("mask_token")
-            call("sed_mlm_apply_bwd_c", g, plan["action"], plan["src_idx"], gx, dtok if dtok is not None else Z(Dd), M, Dd)
-            g = gx
-        if hook is not None:
-            hook("decoder")  # MLM head / context-network / mask_token gradients are final
-        dfbm = grads.get("frame_before_mask")
-        if dfbm is not None:
-            g = g + dfbm.contiguous().float()
-        if ctx.get("nam") is not None:      # norm_after_merge (DASM)
+        return g
+
+    def _trunk_bwd(self, W, ctx, g, G):
+        """norm_after_merge (DASM), the projector merge, the CNN branch, the two projections -> d(pooled) [B tp, D]."""
+        m = self.m
+        B, Tdec, tp = ctx["B"], ctx["Tdec"], ctx["tp"]
+        Dd = m.decoder_dim
+        M = B * Tdec
+        E = lambda *s: torch.empty(*s, dtype=F32, device=g.device)
+        slots, scatter = ctx["gslots"]
+        if ctx.get("nam") is not None:
             nam = ctx["nam"]
             gm = E(B, Tdec, Dd)
             call("sed_layernorm_bwd", g.contiguous().view(M, Dd), nam["x"].view(M, Dd), nam["mean"], nam["rstd"], self.P("norm_after_merge.weight"), 1.0,
                  gm.view(M, Dd), 0, G("norm_after_merge.weight"), G("norm_after_merge.bias"), M, Dd)
             g = gm
-        # projector merge and the two projections
         Tc = ctx["cctx"]["Tc"]
         dP1, dP2 = E(B * tp, Dd), E(B * Tc, Dd)
         call("sed_pmam_merge_bwd", g.contiguous(), ctx["P2"], self.P("merge_weight"), dP1, dP2, G("merge_weight"), B, tp, 1, m.decode_ratio,
@@ -917,74 +860,47 @@ class PmamEngine(SedEngine):
         g16 = self._dw_accum(dP2, ctx["feat"], B * Tc, G("cnn_projector.weight"), G("cnn_projector.bias"))
         dfeat = E(B * Tc, ctx["feat"].shape[1])
         gemm_nt(g16, W["cnn_projector.weight"].wt, EPI_F32, outF=dfeat)
-        if cnn_train:
+        if G("cnn.cnn.conv0.weight") is not None:
             self._cnn_bwd(W, ctx["cctx"], dfeat, B, G, slots)
             if "cnn" in scatter:
                 call("sed_scatter_add_f32", *scatter["cnn"])
         g16 = self._dw_accum(dP1, ctx["pooled"].view(B * tp, D), B * tp, G("transformer_projector.weight"), G("transformer_projector.bias"))
         dpooled = E(B * tp, D)
         gemm_nt(g16, W["transformer_projector.weight"].wt, EPI_F32, outF=dpooled)
-        ectx = ctx["ectx"]
-        N = ectx["N"]
-        # which encoder blocks still need a gradient: everything above the lowest block with a trainable (LoRA) parameter
-        def block_trainable(i):
-            pre = f"backbone.blocks.{i}."
-            return any(p.requires_grad for n, p in m._param_by_name.items() if n.startswith(pre))
-        live = [i for i in range(len(ectx["layers"])) if block_trainable(i)]
-        embed_train = any(m._param_by_name[n].requires_grad for n in ("backbone.patch_embed.proj.weight", "backbone.cls_token"))
-        lowest = 0 if embed_train else (min(live) if live else None)
-        need_dx = lowest is not None
-        genc = None
-        m._at_grad_seen = m.has_at and grads.get("at_out") is not None
-        if m._at_grad_seen:
-            genc = self._at_bwd(W, ctx["actx"], ectx, grads["at_out"].contiguous().float(), G, need_dx=need_dx)
-        if dframe is not None:
-            # DASM: the tagging stream reads the final-norm patch tokens (detect_any_sound.py:350): through backbone.norm into the top of the stack
-            dfull = Z(B, N, D)
-            dfull[:, 2:, :] = dframe
-            genc = E(B, N, D)
-            call("sed_layernorm_bwd", dfull.view(B * N, D), ectx["x_final"], ectx["fmean"], ectx["frstd"], self.P("backbone.norm.weight"), 1.0,
-                 genc.view(B * N, D), 0, G("backbone.norm.weight"), G("backbone.norm.bias"), B * N, D)
-            if not need_dx:
-                genc = None
-        gpool = self._fpool_bwd(W, ectx, dpooled, B, tp, G)
-        if hook is not None:
-            hook("heads")
-        if not need_dx:
-            return
-        if genc is None:
-            genc = Z(B, N, D)
-        s = float(m.lora_scaling)
-        for li in range(len(ectx["layers"]) - 1, lowest - 1, -1):
-            if li + 1 == m.passt_feature_layer:
-                genc.add_(gpool)
-            pre = f"backbone.blocks.{li}."
-            tmp = {}
-            def Gl(name, pre=pre, tmp=tmp):
-                if name.endswith(".weight") and name[:-7] + ".lora_A" in m._param_by_name and G(name[:-7] + ".lora_A") is not None \
-                        and G(name) is None:
-                    base = name[:-7]
-                    if self.lora_skinny and m.lora_r <= 8:
-                        # (`_dw_accum` below turns this into the four skinny products; the gradient of the merged weight is never formed)
-                        return _LoraSlot(self.P(base + ".lora_A").detach(), self.P(base + ".lora_B").detach(), G(base + ".lora_A"),
-                                         G(base + ".lora_B"), m.lora_r, s)
-                    if name not in tmp:
-                        tmp[name] = torch.zeros_like(m._param_by_name[name])
-                    return tmp[name]
+        return dpooled
+
+    def _scan_lowest_trainable(self, G, depth):
+        """From the requires_grad flags (a LoRA block's frozen base weights have no gradient view, its factors do): the lowest block with
+        a trainable parameter; 0 when the patch embedding trains."""
+        pbn = self.m._param_by_name
+        if any(pbn[n].requires_grad for n in ("backbone.patch_embed.proj.weight", "backbone.cls_token")):
+            return 0, True
+        live = {int(n.split(".")[2]) for n, p in pbn.items() if p.requires_grad and n.startswith("backbone.blocks.")}
+        return min((i for i in live if i < depth), default=depth), False
+
+    def _enc_layer_bwd(self, W, ectx, li, g, G):
+        """The block's backward with the LoRA linears' weight gradients redirected: to the factors' gradients through the skinny products
+        of `_dw_accum` (`_LoraSlot`), or through a scratch of the full dW that `sed_lora_grad` projects onto the factors afterwards."""
+        m = self.m
+        s = float(m.lora_scaling) if m.lora_r else 0.0
+        tmp = {}
+
+        def Gl(name):
+            base = name[:-7]
+            if not (name.endswith(".weight") and base + ".lora_A" in m._param_by_name and G(base + ".lora_A") is not None and G(name) is None):
                 return G(name)
-            genc = self._enc_layer_bwd(W, ectx, li, genc, Gl)
-            if tmp:
-                self._join_dw()      # the full dW_eff scratch of a LoRA layer comes from the side stream; sed_lora_grad reads it here
-            for name, dW in tmp.items():
-                base = name[:-7]
-                call("sed_lora_grad", dW, self.P(base + ".lora_A").detach(), self.P(base + ".lora_B").detach(), s, G(base + ".lora_A"),
-                     G(base + ".lora_B"), dW.shape[0], dW.shape[1], m.lora_r)
-            if hook is not None:
-                hook(("block", li))
-        if embed_train:
-            dconv16 = E(B * 12 * tp, D, dt=BF16)
-            call("sed_assemble_tokens_bwd", genc, dconv16, G("backbone.cls_token"), G("backbone.dist_token"), G("backbone.new_pos_embed"),
-                 G("backbone.freq_new_pos_embed"), G("backbone.time_new_pos_embed"), int(ectx["toffsets"][0]), B, tp)
-            self._dw_accum(dconv16, ectx["cols"], B * 12 * tp, G("backbone.patch_embed.proj.weight"), G("backbone.patch_embed.proj.bias"))
-        if hook is not None:
-            hook("embed")
+            if self.lora_skinny and m.lora_r <= 8:
+                # (`_dw_accum` turns this into the four skinny products; the gradient of the merged weight is never formed)
+                return _LoraSlot(self.P(base + ".lora_A").detach(), self.P(base + ".lora_B").detach(), G(base + ".lora_A"),
+                                 G(base + ".lora_B"), m.lora_r, s)
+            if name not in tmp:
+                tmp[name] = torch.zeros_like(m._param_by_name[name])
+            return tmp[name]
+        g = super()._enc_layer_bwd(W, ectx, li, g, Gl)
+        if tmp:
+            self._join_dw()      # the full dW_eff scratch of a LoRA layer comes from the side stream; sed_lora_grad reads it here
+        for name, dW in tmp.items():
+            base = name[:-7]
+            call("sed_lora_grad", dW, self.P(base + ".lora_A").detach(), self.P(base + ".lora_B").detach(), s, G(base + ".lora_A"),
+                 G(base + ".lora_B"), dW.shape[0], dW.shape[1], m.lora_r)
+        return g
