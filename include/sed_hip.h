@@ -584,6 +584,34 @@ int sed_swish_bwd(const float* dy, const float* h, void* dh16, int64_t n, hipStr
 /* out = res + scale * in over n fp32 elements (n % 4 == 0; res nullable; out may alias in or res), out16 (nullable) = bf16 of the result */
 int sed_scale_add_f32(const float* in, const float* res, float* out, void* out16, int64_t n, float scale, hipStream_t stream);
 
+/* ------------------------------------------------------------------ Frequency-wise transformer pooling (csrc/fpool_transformer.hip) */
+/* PaSST_SED(f_pool="frequency_wise_tranformer_encoder"): src/models/pooling.py:18-34 behind src/models/passt/passt_sed.py:199-218.
+ * Sequence build: x fp32 [Bx, 2 + F tp, 768] (token stream of the tapped layer, patch tokens in (f, t) order) -> xs fp32
+ * [Bx tp, 1 + F, 768]: row 0 of every sequence is the tag tag_w + tag_b (linear_emb applied to 1), row 1 + f is out_norm (gamma, beta, eps)
+ * of patch token (f, t).  mean / rstd (nullable together): the LayerNorm statistics [Bx tp (1 + F)] by row of xs (0 in the tag rows). */
+int sed_fpool_seq_build_fwd(const float* x, const float* gamma, const float* beta, float eps, const float* tag_w, const float* tag_b,
+                            float* xs, float* mean, float* rstd, int Bx, int tp, int F, hipStream_t stream);
+/* Its backward: dxs fp32 [Bx tp, 1 + F, 768] -> dx (nullable) fp32 [Bx, 2 + F tp, 768], written whole (cls / dist rows zero); dgamma,
+ * dbeta, dtag [768] (each nullable) += the gradients of out_norm and the sum over the sequences of row 0's gradient.  Two stages in a
+ * fixed order, no atomics: the same bits in every run.  partials: scratch of min(ceil(Bx tp (1 + F) / 4), 256) * 3 * 768 floats. */
+int sed_fpool_seq_build_bwd(const float* dxs, const float* x, const float* mean, const float* rstd, const float* gamma, float* dx,
+                            float* dgamma, float* dbeta, float* dtag, float* partials, int64_t partial_floats, int Bx, int tp, int F,
+                            hipStream_t stream);
+/* frequency_transformer_norm on row 0 of every sequence: xs fp32 [S, N, 768] -> pooled fp32 [S, 768]; mean / rstd [S] nullable together */
+int sed_fpool_rownorm_fwd(const float* xs, const float* gamma, const float* beta, float eps, float* pooled, float* mean, float* rstd,
+                          int S, int N, hipStream_t stream);
+/* Its backward: dxs fp32 [S, N, 768] is written whole (rows 1 .. N-1 zero); dgamma / dbeta (nullable) +=, in a fixed order.
+ * partials: scratch of min(ceil(S / 4), 256) * 2 * 768 floats. */
+int sed_fpool_rownorm_bwd(const float* dpooled, const float* xs, const float* mean, const float* rstd, const float* gamma, float* dxs,
+                          float* dgamma, float* dbeta, float* partials, int64_t partial_floats, int S, int N, hipStream_t stream);
+/* softmax(q k^T 192^-0.5) v of timm's Attention for S sequences of N tokens (2 <= N <= 16) and H heads of 192: qkv [S N, 3 H 192] is the
+ * packed qkv GEMM output (in_kind: 0 bf16, 1 f16, 2 fp32), out the A operand of the proj GEMM (mode 0 bf16 / 1 IEEE half: [S N, H 192];
+ * 4: the split-precision image [S N, 3 H 192] = [hi | lo | hi], as sed_layernorm_fwd writes it).  fp32 arithmetic; one wave owns a
+ * (sequence, head). */
+int sed_attn_short_fwd(const void* qkv, void* out, int S, int N, int H, int in_kind, int mode, hipStream_t stream);
+/* Its backward: dout bf16 [S N, H 192] -> dqkv bf16 [S N, 3 H 192]; the probabilities are recomputed from qkv.  No atomics. */
+int sed_attn_short_bwd(const void* qkv, const void* dout, void* dqkv, int S, int N, int H, int in_kind, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

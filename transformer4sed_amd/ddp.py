@@ -25,6 +25,10 @@ def stage_of(name, depth):
         return "decoder"
     if name.startswith("at_adpater") or name.startswith("out_norm") or name.startswith("backbone.norm") or name.startswith("norm_after_merge"):
         return "heads"
+    # the frequency-wise transformer pooling (passt_sed._FreqTransformerPool): its backward runs inside `_fpool_bwd`, once per window group
+    # and last for the global pass, right before the "heads" hook -- where out_norm, which it shares that stage with, is final too
+    if name.startswith(("f_pool_module.linear_emb.", "f_pool_module.frequency_transformer")):
+        return "heads"
     return "embed"
 
 

@@ -9,6 +9,7 @@ This is the host-side orchestration of the HIP kernels behind `PaSST_SED.forward
 There is no autograd tape inside: `_SedFunction` in passt_sed.py exposes the whole model as a single
 autograd node so that the reference's training loops (loss via torch ops, loss.backward()) keep working.
 """
+import contextlib
 import math
 
 import torch
@@ -24,6 +25,8 @@ from .ops import EPI_F32, EPI_F32_RESID, EPI_BF16, EPI_GELU, EPI_DGELU, EPI_F32_
 D = 768
 H = 12
 NCLS_MAX = 16
+FPOOL_TRANSFORMER = "frequency_wise_tranformer_encoder"     # f_pool value of the frequency-wise transformer pooling ((sic) the reference's spelling)
+FPOOL_HEADS = 4         # its blocks: 4 heads of 192 (src/models/pooling.py:24)
 WCORR_STEP = 8      # `_wcorr_bias`: clip means from every 8th token (1/8 of the extra read)
 
 
@@ -193,6 +196,11 @@ class SedEngine:
             return False        # PaSST_CNN in train mode: the GEMM operand is W + s B A, not the master the residual image is taken from
         return not self.m.training
 
+    def _fpool_split_on(self, save):
+        """Does this pass run the transformer pooling's GEMMs in split precision?  Scored passes do (module in eval mode, nothing saved);
+        training-mode passes run them on plain f16 operands like the encoder blocks."""
+        return self.split and self._wcorr_on(save)
+
     def _lnf_image(self, W, wname, bname, gname, btname):
         """(f16(gamma (.) W), colS, colC) of a Linear that follows a LayerNorm (sed_ln_fold_weight), cached per weight on all four
         masters."""
@@ -285,7 +293,12 @@ class SedEngine:
             names += ["mlm_mlp.0.weight", "mlm_mlp.2.weight"]
         if m.has_at:
             names += ["at_adpater.0.frequency_att.in_proj_weight"]
-        ptrs = tuple(self.P(n).data_ptr() for n in names) + (bool(need_t), self.split)
+        if m.f_pool_name == FPOOL_TRANSFORMER:
+            for i in range(2):
+                p = f"f_pool_module.frequency_transformer.{i}."
+                names += [p + "attn.qkv.weight", p + "attn.proj.weight", p + "mlp.fc1.weight", p + "mlp.fc2.weight"]
+        fp_split = self._fpool_split_on(need_t)         # (`need_t` is the forward's `save`)
+        ptrs = tuple(self.P(n).data_ptr() for n in names) + (bool(need_t), self.split, fp_split)
         if getattr(self, "_wimg_key", None) != ptrs:
             # descriptor table of sed_weight_images: rebuilt only when a master moved (optimizer arenas, .to(device))
             rows, tiles = [], 0
@@ -300,7 +313,7 @@ class SedEngine:
                     ent = _W(torch.empty(n_out, k_in, dtype=self.act, device=w32.device),
                              torch.empty(k_in, n_out, dtype=BF16, device=w32.device))
                     self.cache[n] = ent
-                want_split = self.split and (n.startswith("decoder.") or n.startswith("mlm_mlp"))
+                want_split = self.split and (n.startswith(("decoder.", "mlm_mlp")) or (fp_split and n.startswith("f_pool_module.")))
                 if want_split and (ent.ws is None or ent.ws.device != w32.device):
                     ent.ws = torch.empty(n_out, 3 * k_in, dtype=F16, device=w32.device)
                 rows.append([w32.data_ptr(), ent.wt.data_ptr() if need_t else 0, ent.w.data_ptr(), ent.ws.data_ptr() if want_split else 0,
@@ -522,7 +535,9 @@ class SedEngine:
 
     def _fpool_fwd(self, W, x, Bx, tp, save, ctx):
         """'mean_pool' frequency pooling (passt_sed.py:199-210): out_norm + mean over the frequency rows of the sequence (12, or the
-        kept ones of structured patchout) -> [Bx, tp, D]."""
+        kept ones of structured patchout) -> [Bx, tp, D].  Other values of `f_pool` have a stage pair of their own."""
+        if self.m.f_pool_name == FPOOL_TRANSFORMER:
+            return self._fpool_tr_fwd(W, x, Bx, tp, save, ctx)
         dev = x.device
         F = ctx["F"]
         M = Bx * (2 + F * tp)
@@ -532,6 +547,76 @@ class SedEngine:
         call("sed_fpool_rows_fwd", x, self.P("out_norm.weight"), self.P("out_norm.bias"), 1e-5, pooled, pm, pr, Bx, tp, F)
         if save:
             ctx.update(pool_x=x, pool_mean=pm, pool_rstd=pr)
+        return pooled
+
+    def _fpool_tr_fwd(self, W, x, Bx, tp, save, ctx):
+        """Frequency-wise transformer pooling (src/models/pooling.py:18-34 behind passt_sed.py:199-218): out_norm, then per (clip or
+        window, time column) the sequence [tag | F frequency rows] through two pre-LN timm blocks of 4 heads (LayerNorm eps 1e-5, qkv
+        without a bias), the closing LayerNorm, and row 0 of every sequence -> [Bx, tp, D].  The residual stream is fp32 [S N, D] with
+        S = Bx tp, N = 1 + F; the GEMMs and block LayerNorms are the model's own, on M = S N rows.
+        Operand precision (`_fpool_split_on`): training-mode passes run the four GEMMs of a block on plain f16 operands like the encoder
+        blocks; scored passes (module in eval mode, nothing saved) run them in split precision like the context network's
+        ([hi | lo | hi] activations against [hi | hi | lo] weight images, which `_weights` rewrites every forward) -- qkv then leaves
+        its GEMM in fp32 and the attention kernel writes the split image of its output itself.  DESIGN.md section 3 has the measured
+        posterior errors of both forms."""
+        dev = x.device
+        F = ctx["F"]
+        N, S = 1 + F, Bx * tp
+        M = S * N
+        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        A16 = self.act
+        f16 = 1 if A16 == F16 else 0
+        SP = self._fpool_split_on(save)
+        mode = 4 if SP else f16
+        img = lambda k=D: E(M, 3 * k, dt=F16) if SP else E(M, k, dt=A16)       # operand image of an [M, k] activation
+        wk = (lambda n: W[n].ws) if SP else (lambda n: W[n].w)
+        pre = "f_pool_module."
+        cur = E(M, D)
+        pm, pr = (E(M), E(M)) if save else (None, None)
+        call("sed_fpool_seq_build_fwd", x, self.P("out_norm.weight"), self.P("out_norm.bias"), 1e-5, self.P(pre + "linear_emb.weight"),
+             self.P(pre + "linear_emb.bias"), cur, pm, pr, Bx, tp, F)
+        layers = []
+        with (ops.split_precision() if SP else contextlib.nullcontext()):
+            for i in range(2):
+                p = f"{pre}frequency_transformer.{i}."
+                stats = lambda: (E(M), E(M)) if save else (None, None)
+                h16 = img()
+                mean1, rstd1 = stats()
+                call("sed_layernorm_fwd", cur, self.P(p + "norm1.weight"), self.P(p + "norm1.bias"), 1e-5, 1.0, h16, None, mean1, rstd1, M, D, mode)
+                if SP:
+                    qkv = E(M, 3 * D)
+                    gemm_nt(h16, wk(p + "attn.qkv.weight"), EPI_F32, outF=qkv)
+                else:
+                    qkv = E(M, 3 * D, dt=A16)
+                    gemm_nt(h16, wk(p + "attn.qkv.weight"), EPI_BF16, outH=qkv)
+                o16 = img()
+                call("sed_attn_short_fwd", qkv, o16, S, N, FPOOL_HEADS, o_kind(qkv), mode)
+                x_mid = E(M, D) if save else cur        # (nothing saved: the stream is updated in place)
+                gemm_nt(o16, wk(p + "attn.proj.weight"), EPI_F32_RESID, bias=self.P(p + "attn.proj.bias"), res=cur, outF=x_mid)
+                h2 = img()
+                mean2, rstd2 = stats()
+                call("sed_layernorm_fwd", x_mid, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-5, 1.0, h2, None, mean2, rstd2, M, D, mode)
+                hpre = E(M, 4 * D, dt=BF16 if save else A16)      # (GELU pre-activation: read by the backward only)
+                if SP:
+                    act = E(M, 4 * D)
+                    gemm_nt(h2, wk(p + "mlp.fc1.weight"), EPI_GELU32, bias=self.P(p + "mlp.fc1.bias"), outH=hpre, outF=act)
+                    act = split3(act, M, 4 * D)         # forward operand and (first third) weight-gradient operand of fc2
+                else:
+                    act = E(M, 4 * D, dt=A16)
+                    gemm_nt(h2, wk(p + "mlp.fc1.weight"), EPI_GELU, bias=self.P(p + "mlp.fc1.bias"), outH=hpre, outH2=act)
+                x_out = E(M, D) if save else x_mid
+                gemm_nt(act, wk(p + "mlp.fc2.weight"), EPI_F32_RESID, bias=self.P(p + "mlp.fc2.bias"), res=x_mid, outF=x_out)
+                if save:
+                    # (split images [M, 3 k]: the first third is the f16 operand of the weight gradients)
+                    layers.append(dict(x_in=cur, h16=h16, qkv=qkv, o16=o16, x_mid=x_mid, h2=h2, hpre=hpre, act=act, mean1=mean1, rstd1=rstd1,
+                                       mean2=mean2, rstd2=rstd2))
+                cur = x_out
+        pooled = E(Bx, tp, D)
+        fm, fr = (E(S), E(S)) if save else (None, None)
+        call("sed_fpool_rownorm_fwd", cur, self.P(pre + "frequency_transformer_norm.weight"), self.P(pre + "frequency_transformer_norm.bias"),
+             1e-5, pooled, fm, fr, S, N)
+        if save:
+            ctx.update(pool_x=x, pool_mean=pm, pool_rstd=pr, pool_tr=dict(layers=layers, x_out=cur, fmean=fm, frstd=fr))
         return pooled
 
     # ------------------------------------------------------------------ context network
@@ -1117,6 +1202,8 @@ class SedEngine:
     def _fpool_bwd(self, W, ectx, dpooled, G, need_dx):
         """Backward of `_fpool_fwd`; -> its gradient at the encoder residual stream of the tapped layer [B, N, D] (cls / dist rows
         zero), or None when `need_dx` is false and the form can skip it."""
+        if self.m.f_pool_name == FPOOL_TRANSFORMER:
+            return self._fpool_tr_bwd(W, ectx, dpooled, G, need_dx)
         B, N, tp, F = ectx["B"], ectx["N"], ectx["tp"], ectx["F"]
         dev = dpooled.device
         Z = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
@@ -1125,6 +1212,55 @@ class SedEngine:
         pool_dx = gpool if need_dx else Z(B, N, D)
         call("sed_fpool_rows_bwd", dpooled.contiguous(), ectx["pool_x"], ectx["pool_mean"], ectx["pool_rstd"], self.P("out_norm.weight"),
              dtok_tmp, pool_dx, G("out_norm.weight"), G("out_norm.bias"), B, tp, F)
+        return gpool
+
+    def _fpool_tr_bwd(self, W, ectx, dpooled, G, need_dx):
+        """Backward of `_fpool_tr_fwd`.  A frozen module (finetune1: `G` names none of its tensors) is still walked: out_norm and the
+        encoder lie under it."""
+        B, tp, F = ectx["B"], ectx["tp"], ectx["F"]
+        T = ectx.pop("pool_tr")
+        N, S = 1 + F, B * tp
+        M = S * N
+        dev = dpooled.device
+        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        pre = "f_pool_module."
+        part = getattr(self, "_fpool_ws", None)       # per-workgroup partials of the parameter-gradient reductions (see include/sed_hip.h)
+        if part is None or part.device != dev:
+            part = self._fpool_ws = torch.empty(256 * 3 * D, dtype=F32, device=dev)
+        g = E(M, D)
+        call("sed_fpool_rownorm_bwd", dpooled.contiguous(), T["x_out"], T["fmean"], T["frstd"], self.P(pre + "frequency_transformer_norm.weight"),
+             g, G(pre + "frequency_transformer_norm.weight"), G(pre + "frequency_transformer_norm.bias"), part, part.numel(), S, N)
+        for i in (1, 0):
+            p = f"{pre}frequency_transformer.{i}."
+            L = T["layers"][i]
+            # ---- MLP branch: x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))
+            dln = self._mlp_bwd(W, p + "mlp.fc1", p + "mlp.fc2", g, L["h2"], L["hpre"], L["act"], M, G, residual=None)
+            call("sed_layernorm_bwd", dln, L["x_mid"], L["mean2"], L["rstd2"], self.P(p + "norm2.weight"), 1.0, g, 1,
+                 G(p + "norm2.weight"), G(p + "norm2.bias"), M, D)
+            del dln
+            # ---- attention branch: x_mid = x_in + proj(attn(LN1(x_in)))
+            g16 = self._dw_accum(g, L["o16"], M, G(p + "attn.proj.weight"), G(p + "attn.proj.bias"), k_in=D)
+            do16 = E(M, D, dt=BF16)
+            gemm_nt(g16, W[p + "attn.proj.weight"].wt, EPI_BF16, outH=do16)
+            dqkv = E(M, 3 * D, dt=BF16)
+            call("sed_attn_short_bwd", L["qkv"], do16, dqkv, S, N, FPOOL_HEADS, o_kind(L["qkv"]))
+            del do16
+            self._dw_accum(dqkv, L["h16"], M, G(p + "attn.qkv.weight"), None, k_in=D)
+            dln = E(M, D)
+            gemm_nt(dqkv, W[p + "attn.qkv.weight"].wt, EPI_F32, outF=dln)
+            call("sed_layernorm_bwd", dln, L["x_in"], L["mean1"], L["rstd1"], self.P(p + "norm1.weight"), 1.0, g, 1,
+                 G(p + "norm1.weight"), G(p + "norm1.bias"), M, D)
+            T["layers"][i] = None       # free saved activations
+        # ---- the sequence build: out_norm, and the tag row (linear_emb applied to 1: weight[:, 0] and bias get the same gradient)
+        gw, gb = G(pre + "linear_emb.weight"), G(pre + "linear_emb.bias")
+        dtag = torch.zeros(D, dtype=F32, device=dev) if (gw is not None or gb is not None) else None
+        gpool = E(B, ectx["N"], D) if need_dx else None
+        call("sed_fpool_seq_build_bwd", g, ectx["pool_x"], ectx["pool_mean"], ectx["pool_rstd"], self.P("out_norm.weight"), gpool,
+             G("out_norm.weight"), G("out_norm.bias"), dtag, part, part.numel(), B, tp, F)
+        if gw is not None:
+            gw.view(D).add_(dtag)
+        if gb is not None:
+            gb.add_(dtag)
         return gpool
 
     def _frame_norm_bwd(self, ectx, dframe, G, need_dx):

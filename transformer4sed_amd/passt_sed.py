@@ -13,7 +13,7 @@ from collections.abc import Sequence
 import torch
 import torch.nn as nn
 
-from .engine import SedEngine, window_starts, D, H
+from .engine import SedEngine, window_starts, D, H, FPOOL_TRANSFORMER
 from .frontend import PasstFeatureExtractor
 
 
@@ -276,6 +276,19 @@ class _AttnPool(_Holder):
         self.frequency_att = nn.MultiheadAttention(embed_dim=dim, num_heads=heads, batch_first=True)
 
 
+class _FreqTransformerPool(_Holder):
+    """Parameter layout of `FrequencyWiseTranformerPooling` (src/models/pooling.py:18-25): the tag embedding `linear_emb`, two timm
+    0.4.5 `Block`s of 4 heads (qkv without a bias, LayerNorm eps 1e-5) and the closing LayerNorm; torch's default initialisation."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.linear_emb = nn.Linear(1, dim)
+        self.frequency_transformer = nn.ModuleList([_Block(dim, 4, 1e-5) for _ in range(2)])
+        for blk in self.frequency_transformer:
+            blk.attn.qkv = nn.Linear(dim, 3 * dim, bias=False)
+        self.frequency_transformer_norm = nn.LayerNorm(dim)
+
+
 class _Hookable(nn.Module):
     def forward(self, x, *a):
         return x
@@ -359,7 +372,7 @@ class PaSST_SED(SEDModel):
             if f_pool not in ("mean_pool", "attention"): unsupported.append(f"f_pool={f_pool!r}")
         else:
             if embed_dim != D or decoder_dim != D: unsupported.append("embed_dim/decoder_dim != 768")
-            if f_pool != "mean_pool": unsupported.append(f"f_pool={f_pool!r}")
+            if f_pool not in ("mean_pool", FPOOL_TRANSFORMER): unsupported.append(f"f_pool={f_pool!r}")
             if lora_config is not None: unsupported.append("LoRA")
         if decoder not in (("transformerXL",) if _pmam else ("transformerXL", "conformer")):
             unsupported.append(f"decoder={decoder!r}" + (" (the conformer decoder exists for PaSST_SED only)" if decoder == "conformer" else ""))
@@ -396,6 +409,8 @@ class PaSST_SED(SEDModel):
         self.out_norm = nn.LayerNorm(embed_dim)
         if f_pool == "attention":
             self.f_pool_module = _AttnPool(embed_dim, 6)
+        elif f_pool == FPOOL_TRANSFORMER:
+            self.f_pool_module = _FreqTransformerPool(embed_dim)
         self.interpolate_module = _Hookable()
         self.slide_window_layer = nn.Identity()
         self.mlm = mlm

@@ -203,6 +203,61 @@ def conformer_state_dict_np(tag="wc0", dec_layers=2, tap_scale=0.35, **kw):
 
 
 # --------------------------------------------------------------------------------------------------
+# MAT-SED with the frequency-wise transformer pooling, PaSST_SED(f_pool="frequency_wise_tranformer_encoder") (reference definition
+# sites: src/models/pooling.py:18-34, src/models/passt/passt_sed.py:146-154; the blocks are timm 0.4.5 `Block`s with 4 heads)
+# --------------------------------------------------------------------------------------------------
+def fpool_transformer_shapes(D=768, blocks=2, mlp_ratio=4):
+    p, s = "f_pool_module.", {}
+    s[p + "linear_emb.weight"] = (D, 1)
+    s[p + "linear_emb.bias"] = (D,)
+    for i in range(blocks):
+        b = f"{p}frequency_transformer.{i}."
+        s[b + "norm1.weight"] = (D,)
+        s[b + "norm1.bias"] = (D,)
+        s[b + "attn.qkv.weight"] = (3 * D, D)       # (qkv_bias=False: timm 0.4.5's default)
+        s[b + "attn.proj.weight"] = (D, D)
+        s[b + "attn.proj.bias"] = (D,)
+        s[b + "norm2.weight"] = (D,)
+        s[b + "norm2.bias"] = (D,)
+        s[b + "mlp.fc1.weight"] = (mlp_ratio * D, D)
+        s[b + "mlp.fc1.bias"] = (mlp_ratio * D,)
+        s[b + "mlp.fc2.weight"] = (D, mlp_ratio * D)
+        s[b + "mlp.fc2.bias"] = (D,)
+    s[p + "frequency_transformer_norm.weight"] = (D,)
+    s[p + "frequency_transformer_norm.bias"] = (D,)
+    return s
+
+
+def fpool_transformer_state_dict_np(tag="wft768", dec_layers=2, qkv_gain=1.0, tag_scale=1.0, **kw):
+    """`matsed_state_dict_np` (same tag, `dec_layers` Transformer-XL blocks) plus the 26 tensors of the frequency-wise transformer
+    pooling under `f_pool_module.`.  LayerNorm weights near 1; every linear weight at unit gain, qkv included (`qkv_gain`: attention
+    logits of about unit variance -- torch's default initialisation of the module has gain 0.58); the tag row
+    `linear_emb.weight[:, 0] + bias` uniform in about +-tag_scale, the size of the normalised tokens it sits beside.
+    tools/gen_fpool_transformer_golden.py asserts that the posteriors move by >= 20e-3 when the attention is made uniform and when the
+    tag is zeroed (measured 0.25 / 0.77).  The encoder's gain of 1.6 is NOT used for qkv here: the pooled frame is row 0 of the
+    sequence, which sees the encoder's tokens only through the attention, and the sharper the softmax the fewer rows it averages.  In
+    the reference itself, on the CPU, a relative perturbation of 3e-4 of out_norm's output moves `strong` (temp_w 0.5) by 2.1e-4 under
+    mean pooling, 2.1e-4 with this module at gain 1.0 and 7.2e-4 at gain 1.6 -- at 1.6 the fixture would measure
+    the 16-bit encoder against a bound that was set for a 12-row average, not this module; the sharp case has a fixture of its
+    own, held to 1e-3 times the reference's recorded noise gain (tools/gen_fpool_transformer_golden.py, `gen_sharp`)."""
+    D = kw.get("embed_dim", 768)
+    out = matsed_state_dict_np(tag=tag, dec_layers=dec_layers, **kw)
+    for name, shp in fpool_transformer_shapes(D).items():
+        key = f"{tag}/{name}"
+        if name.endswith("linear_emb.weight"):
+            w = tag_scale * det_uniform(key, shp)
+        elif name.endswith(".bias"):
+            w = 0.1 * det_uniform(key, shp)
+        elif "norm" in name:
+            w = 1.0 + 0.2 * det_uniform(key, shp)
+        else:
+            gain = qkv_gain if "qkv" in name else 1.0
+            w = det_uniform(key, shp) * (gain * math.sqrt(3.0 / shp[-1]))
+        out[name] = w.astype(np.float32)
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # PMAM `PaSST_CNN` state_dict (SURVEY.md section 8(f) rank 3; reference definition sites:
 # src/models/cnn_transformer/passt_cnn.py:11-20, src/models/cnn/base.py:62-98, src/models/lora/layers.py:107-116,
 # src/models/passt/passt_lora.py:116-125, src/models/pooling.py:39-43; values of config/pmam/post_pretrain.yaml:47-80)
