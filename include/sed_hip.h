@@ -612,6 +612,34 @@ int sed_attn_short_fwd(const void* qkv, void* out, int S, int N, int H, int in_k
 /* Its backward: dout bf16 [S N, H 192] -> dqkv bf16 [S N, 3 H 192]; the probabilities are recomputed from qkv.  No atomics. */
 int sed_attn_short_bwd(const void* qkv, const void* dout, void* dqkv, int S, int N, int H, int in_kind, hipStream_t stream);
 
+/* ---- frequency-dynamic convolution of the PaSST_CNN branch (cnn_name "FDY-CNN"; src/models/cnn/FDY_cnn.py:7-116, pool_dim 'freq', four
+ * basis kernels; csrc/fdy_cnn.hip).  R = B H frame rows; every reduction runs in a fixed order (no float atomics). */
+/* FDY_cnn.py:97  x.mean(dim=3): X 16-bit NHWC [R, W, Cp] (channels C.. padding) -> pm fp32 [R, C] */
+int sed_fdy_freq_mean(const void* X, int f16, float* pm, int64_t R, int W, int C, int Cp, hipStream_t stream);
+/* FDY_cnn.py:107  conv1d1 (cin -> hid, kernel 3, padding 1 along the frames, no bias): pm [B H, cin], W1 [hid, cin, 3] -> u [B H, hid];
+ * part (nullable: eval) double [ceil(B H / 16), 2, hid]: per-workgroup sums of u and u^2 for the BatchNorm1d batch statistics */
+int sed_fdy_attn_taps(const float* pm, const float* W1, float* u, double* part, int B, int H, int cin, int hid, hipStream_t stream);
+/* FDY_cnn.py:108-116  bn (batch statistics from `part`, running statistics updated by torch's rule: momentum, unbiased variance; part null:
+ * running statistics), relu, conv1d2 (W2 [4, hid], b2 [4]), softmax(. / temperature) -> att [R, 4]; aff [3, hid] = mean | rstd | gamma rstd */
+int sed_fdy_attn_softmax(const float* u, const double* part, const float* gamma, const float* beta, float* run_mean, float* run_var,
+                         const float* W2, const float* b2, float temperature, double momentum, double eps, float* aff, float* att,
+                         int R, int hid, hipStream_t stream);
+/* FDY_cnn.py:53-61  Y[m, o] = sum_k att[m / W, k] Y4[m, k co + o]: Y4 fp32 [M, ld4] (the GEMM of the patch matrix with the [4 co, 9 cin]
+ * weight image), Y fp32 [M, ldy] (columns co.. zero) */
+int sed_fdy_mix_fwd(const float* Y4, int ld4, const float* att, float* Y, int ldy, int64_t M, int W, int co, hipStream_t stream);
+/* its backward: dY bf16 [R W, ldo] -> dY4 bf16 [R W, ldg4] = att (x) dY (columns 4 co.. zero), da fp32 [R, 4] = sum_{w, o} dY Y4_k */
+int sed_fdy_mix_bwd(const void* dY, int ldo, const float* Y4, int ld4, const float* att, void* dY4, int ldg4, float* da, int64_t R,
+                    int W, int co, hipStream_t stream);
+/* backward of sed_fdy_attn_softmax and sed_fdy_attn_taps: da [B H, 4] -> dpm [B H, cin]; gW1 [hid, cin, 3], ggamma / gbeta [hid], gW2 [4, hid],
+ * gb2 [4] (each nullable) +=.  batch_stats: the forward ran on batch statistics.  Scratch: dz fp32 [B H, hid], part double
+ * [ceil(B H / 16), 6 hid + 4], ws fp32 of at least ceil4(6 hid + 4) + clamp(B H / 128, 1, 32) * 3 hid cin floats */
+int sed_fdy_attn_bwd(const float* da, const float* att, const float* u, const float* aff, const float* pm, const float* W1,
+                     const float* beta, const float* W2, float temperature, int batch_stats, float* dz, double* part, float* ws,
+                     int64_t ws_floats, float* dpm, float* gW1, float* ggamma, float* gbeta, float* gW2, float* gb2, int B, int H,
+                     int cin, int hid, hipStream_t stream);
+/* backward of sed_fdy_freq_mean onto the input gradient sed_col2im3x3 wrote: dX fp32 [R, W, C] += dpm [R, C] / W */
+int sed_fdy_mean_bwd_add(float* dX, const float* dpm, int64_t R, int W, int C, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -580,6 +580,8 @@ class DASM(PaSST_CNN):
         if ap["out_type"] != "sigmoid": bad.append(f"out_type={ap['out_type']!r}")
         if ap["at_decoder_layer"] < 1: bad.append("at_decoder_layer < 1")
         if bp["pretrain_model_path"] is not None: bad.append("pretrain_model_path (load a state_dict instead)")
+        # (detect_any_sound.py builds `CNN(**cnn_param)`: the reference's DASM has no other CNN branch)
+        if (cnn_param or {}).get("cnn_name", "base") != "base": bad.append(f"cnn_name={cnn_param['cnn_name']!r}")
         if bad:
             raise NotImplementedError("the HIP DASM path covers the text- / audio-query configuration only; unsupported: " + ", ".join(bad))
         super().__init__(passt_sed_param=dict(passt_feature_layer=bp["passt_feature_layer"], class_num=class_num, f_pool="attention",

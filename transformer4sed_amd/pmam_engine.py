@@ -151,21 +151,30 @@ class PmamEngine(SedEngine):
             vecs.append((("dec", i, "v"), p + "attn.pos_bias_v", self._plan("uv", P(p + "attn.pos_bias_v").shape, dev, uv)))
         geo = []
         cin = 1
+        dynamic = getattr(m, "cnn_dynamic", None) or (False,) * len(m.cnn_filters)
         for i, co in enumerate(m.cnn_filters):
             Np = pad128(co)
             Kp = 64 if i == 0 else pad128(9 * cin)
             Cp = max(64, co)
             cw, gw = f"cnn.cnn.conv{i}.weight", f"cnn.cnn.cg{i}.linear.weight"
-            mat(cw, cw, plan=self._plan(("conv", Np, Kp), P(cw).shape, dev,
-                                        lambda w, k, Np=Np, Kp=Kp: pad2(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1), Np, Kp)))
+            # a dynamic layer's four basis kernels [4, co, ci, 3, 3] are one [4 co, 9 ci] operand: rows k co + o (FDY_cnn.py:44)
+            dyn = bool(dynamic[i])
+            Nc = pad128(4 * co) if dyn else Np
+            mat(cw, cw, plan=self._plan(("conv", Nc, Kp), P(cw).shape, dev,
+                                        lambda w, k, Nc=Nc, Kp=Kp: pad2(w.reshape(-1, *w.shape[-3:]).permute(0, 2, 3, 1).reshape(w.numel() // (9 * w.shape[-3]), -1), Nc, Kp)))
             mat(gw, gw, plan=self._plan(("gate", Np, Cp), P(gw).shape, dev, lambda w, k, Np=Np, Cp=Cp: pad2(w, Np, Cp)))
             # backward operand of the gate GEMM: [Np (N), ldg (K)] = W_gate^T, zero padded, bf16 (ldg: row width of the gradient images)
             ldg = 64 if co <= 64 else Np
             mat(gw + "#T", gw, plan=self._plan(("gateT", Np, ldg), P(gw).shape, dev, lambda w, k, Np=Np, ldg=ldg: pad2(w.t(), Np, ldg)), kind="bf16")
             bplan = lambda n, Np=Np: self._plan(("b", Np), P(n).shape, dev, lambda b, k: pad2(b.view(1, -1), 1, Np).view(-1))
-            vecs.append((("cnn", i, "bias"), f"cnn.cnn.conv{i}.bias", bplan(f"cnn.cnn.conv{i}.bias")))
+            if not dyn:      # (Dynamic_conv2d has no bias, FDY_cnn.py:145-147)
+                vecs.append((("cnn", i, "bias"), f"cnn.cnn.conv{i}.bias", bplan(f"cnn.cnn.conv{i}.bias")))
             vecs.append((("cnn", i, "gbias"), f"cnn.cnn.cg{i}.linear.bias", bplan(f"cnn.cnn.cg{i}.linear.bias")))
-            geo.append(dict(Np=Np, Kp=Kp, Cp=Cp, cin=cin, co=co, ldg=ldg))
+            geo.append(dict(Np=Np, Kp=Kp, Cp=Cp, cin=cin, co=co, ldg=ldg, dyn=dyn))
+            if dyn:
+                # Y4 [pixels, ld4] fp32: 64 columns for 16 filters (the GEMM writes only the valid columns), the padded width otherwise;
+                # ldg4: row width of the bf16 gradient operand a (x) dY, as ldg for the static layers
+                geo[-1].update(Nc=Nc, ld4=64 if 4 * co == 64 else Nc, ldg4=64 if 4 * co <= 64 else Nc, hid=max(cin // 4, 4))
             cin = co
         self._specs, self._specs_key = (mats, vecs, geo), key
         return self._specs
@@ -255,7 +264,7 @@ class PmamEngine(SedEngine):
         vdesc, vn, vblocks, _, views = self._vimg
         call("sed_gather_f32", vdesc, vn, vblocks)
         self.dec_aux = [dict(bin=views[("dec", i, "bin")], u=views[("dec", i, "u")], v=views[("dec", i, "v")]) for i in range(m.decoder_layer_num)]
-        self.cnn_aux = [dict(g, bias=views[("cnn", i, "bias")], gbias=views[("cnn", i, "gbias")],
+        self.cnn_aux = [dict(g, bias=views.get(("cnn", i, "bias")), gbias=views[("cnn", i, "gbias")],
                              wtg=self.cache[f"cnn.cnn.cg{i}.linear.weight#T"].w if need_t else None) for i, g in enumerate(geo)]
         return self.cache
 
@@ -307,7 +316,8 @@ class PmamEngine(SedEngine):
         sums = torch.zeros(nl, 2, cmax, device=dev) if train else None      # batch-statistics sums of every layer: one fill
         aff = E(nl, 4, cmax)                                                # a | b | ah | bh of every layer (saved for the backward)
         if train:
-            torch._foreach_add_([m._buffer_by_name[f"cnn.cnn.batchnorm{i}.num_batches_tracked"] for i in range(nl)], 1)
+            torch._foreach_add_([m._buffer_by_name[f"cnn.cnn.batchnorm{i}.num_batches_tracked"] for i in range(nl)] +
+                                [m._buffer_by_name[f"cnn.cnn.conv{i}.attention.bn.num_batches_tracked"] for i in range(nl) if self.cnn_aux[i]["dyn"]], 1)
         gen_masks = None
         if train and m.conv_dropout > 0 and drop_masks is None:
             # keep-masks of every layer from one launch.  The seed comes from a generator of this engine's own (seeded once from
@@ -341,7 +351,9 @@ class PmamEngine(SedEngine):
                     call("sed_conv0_im2col", mel, col, B, T, f16)
                 else:
                     call("sed_conv3x3_im2col", X, col, B, Hc, Wc, cin, max(64, cin), Kp)
-                if ldy < Np:
+                if aux["dyn"]:
+                    dynctx = self._fdy_mix_fwd(W, i, aux, X, col, Y, ldy, B, Hc, Wc, train)
+                elif ldy < Np:
                     gemm_nt_cols(col, W[f"cnn.cnn.conv{i}.weight"].w, EPI_F32, co, bias=aux["bias"], outF=Y)
                 else:
                     gemm_nt(col, W[f"cnn.cnn.conv{i}.weight"].w, EPI_F32, bias=aux["bias"], outF=Y)
@@ -388,11 +400,64 @@ class PmamEngine(SedEngine):
                 call("sed_cg_pool", Y, ldy, a, b, L, ldy, mask, float(scale), Xn, feat, B, Hc, Wc, co, Cpo, ph, pw, f16)
             if save:
                 layers.append(dict(col=col, mel=mel if direct0 else None, Y=Y, a=a, b=b, ah=ah, bh=bh, Z=Z, L=L, mask=mask, scale=scale, H=Hc,
-                                   W=Wc, ldy=ldy))
+                                   W=Wc, ldy=ldy, dyn=dynctx if aux["dyn"] else None))
             X = Xn
             Hc, Wc = Hc // ph, Wc // pw
         assert Wc == 1
         return feat, dict(layers=layers, Tc=Hc)
+
+    def _fdy_mix_fwd(self, W, i, aux, X, col, Y, ldy, B, Hc, Wc, train):
+        """The convolution of a dynamic layer (FDY_cnn.py:34-63) into Y: the attention head on the frequency mean of the layer's input X
+        (train: BatchNorm1d batch statistics, running statistics updated by torch's rule with momentum 0.1), the four basis convolutions
+        as one GEMM of the patch matrix, and the per-frame mixing.  -> what the backward needs (Y4 is kept in fp32)."""
+        m = self.m
+        dev = col.device
+        co, cin, hid, ld4 = aux["co"], aux["cin"], aux["hid"], aux["ld4"]
+        R, Mi = B * Hc, B * Hc * Wc
+        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        pre = f"cnn.cnn.conv{i}.attention."
+        pm, u, aff1, att = E(R, cin), E(R, hid), E(3, hid), E(R, 4)
+        call("sed_fdy_freq_mean", X, is_f16(X), pm, R, Wc, cin, X.shape[-1])
+        part = E((R + 15) // 16 * 2 * hid, dt=torch.float64) if train else None
+        call("sed_fdy_attn_taps", pm, self.P(pre + "conv1d1.weight").detach(), u, part, B, Hc, cin, hid)
+        call("sed_fdy_attn_softmax", u, part, self.P(pre + "bn.weight").detach(), self.P(pre + "bn.bias").detach(),
+             m._buffer_by_name[pre + "bn.running_mean"], m._buffer_by_name[pre + "bn.running_var"], self.P(pre + "conv1d2.weight").detach(),
+             self.P(pre + "conv1d2.bias").detach(), float(m.cnn_temperature), 0.1, 1e-5, aff1, att, R, hid)
+        Y4 = E(Mi, ld4)
+        if ld4 < aux["Nc"]:
+            gemm_nt_cols(col, W[f"cnn.cnn.conv{i}.weight"].w, EPI_F32, ld4, outF=Y4)
+        else:
+            gemm_nt(col, W[f"cnn.cnn.conv{i}.weight"].w, EPI_F32, outF=Y4)
+        call("sed_fdy_mix_fwd", Y4, ld4, att, Y, ldy, Mi, Wc, co)
+        return dict(pm=pm, u=u, aff=aff1, att=att, Y4=Y4, train=bool(train))
+
+    def _fdy_mix_bwd(self, W, i, aux, L, dY16, B, G, slots):
+        """Backward of `_fdy_mix_fwd` from dY (bf16 [pixels, ldo]): the weight gradient of the four basis kernels into its slot, the input
+        gradient through the patch matrix, the attention head's parameter gradients, and the head's path into the input gradient."""
+        dev = dY16.device
+        co, cin, hid, ld4, ldg4, Kp = aux["co"], aux["cin"], aux["hid"], aux["ld4"], aux["ldg4"], aux["Kp"]
+        Hc, Wc, D = L["H"], L["W"], L["dyn"]
+        R, Mi = B * Hc, B * Hc * Wc
+        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        pre = f"cnn.cnn.conv{i}.attention."
+        dY4, da = E(Mi, ldg4, dt=BF16), E(R, 4)
+        call("sed_fdy_mix_bwd", dY16, dY16.shape[1], D["Y4"], ld4, D["att"], dY4, ldg4, da, R, Wc, co)
+        self._dw_swapped(dY4, L["col"], Mi, 4 * co, 9 * cin, out=(slots[("conv", i)], slots[("conv_b", i)]), n_img=ldg4)
+        dcol = E(Mi, Kp, dt=BF16)
+        gemm_nt(dY4, W[f"cnn.cnn.conv{i}.weight"].wt, EPI_BF16, outH=dcol, K=ldg4)
+        dout = E(B, Hc, Wc, cin)
+        call("sed_col2im3x3", dcol, Kp, dout, B, Hc, Wc, cin)
+        del dcol, dY4
+        P6 = 6 * hid + 4
+        ws = E((P6 + 3) // 4 * 4 + max(1, min(32, R // 128)) * 3 * hid * cin)
+        part = E((R + 15) // 16 * P6, dt=torch.float64)
+        dz, dpm = E(R, hid), E(R, cin)
+        call("sed_fdy_attn_bwd", da, D["att"], D["u"], D["aff"], D["pm"], self.P(pre + "conv1d1.weight").detach(), self.P(pre + "bn.bias").detach(),
+             self.P(pre + "conv1d2.weight").detach(), float(self.m.cnn_temperature), 1 if D["train"] else 0, dz, part, ws, ws.numel(), dpm,
+             G(pre + "conv1d1.weight"), G(pre + "bn.weight"), G(pre + "bn.bias"), G(pre + "conv1d2.weight"), G(pre + "conv1d2.bias"),
+             B, Hc, cin, hid)
+        call("sed_fdy_mean_bwd_add", dout, dpm, R, Wc, cin)
+        return dout
 
     # ------------------------------------------------------------------ 384-wide context network on the 64-wide attention kernels
     @in_split_precision
@@ -566,7 +631,9 @@ class PmamEngine(SedEngine):
 
     def _dw_swapped_tn(self, M, n, k):
         """Does `_dw_swapped` run the TN kernel for these shapes (gradient image laid out [n, k]) or the transposed-copy path ([k, n])?"""
-        return bool(self.dw_tn and M >= 1024 and dw_tn_ok(M, n, k))
+        # (below 1024 rows the transposed-copy path is the cheaper one -- but its split-K GEMM needs both widths to fill a 128-wide tile:
+        #  the 64-wide images of the narrow layers stay on the TN kernel at any row count)
+        return bool(self.dw_tn and (M >= 1024 or n < 128 or k < 128) and dw_tn_ok(M, n, k))
 
     def _dw_swapped(self, dy16, x, M, n_valid, k_valid, out=None, k_img=None, n_img=None):
         """(dy^T x)^T = x^T dy for operand widths that are not multiples of 128 on the x side: returns fp32 [k, n] and the fp32 column
@@ -616,7 +683,7 @@ class PmamEngine(SedEngine):
         gemm_dw(xT, gT, gWT)
         return gWT, csum
 
-    def _grad_slots(self, B, dev, G, dec_train, cnn_train):
+    def _grad_slots(self, B, dev, G, dec_train, cnn_train, T=1000):
         """Gradient images of every padded weight / vector of one backward, as views of ONE zeroed fp32 arena, and the two
         `sed_scatter_add_f32` tables (context network, CNN branch) that return them to the masters' gradients through the forward
         plans -- scale sqrt(2) on the K / P rows, nothing from the padding.  Replaces a `zeros` per image and an `add_` of a sliced /
@@ -637,28 +704,31 @@ class PmamEngine(SedEngine):
                           ("dec", ("du", li), Dp, p + "attn.pos_bias_u", pl("uv", p + "attn.pos_bias_u"), Dp, Dp, 0, 1),
                           ("dec", ("dv", li), Dp, p + "attn.pos_bias_v", pl("uv", p + "attn.pos_bias_v"), Dp, Dp, 0, 1)]
         if cnn_train:
-            Hc, Wc = 1000, 128
+            Hc, Wc = T, 128
             for i, g in enumerate(geo):
                 co, Np, Kp, Cp, cin, ldg = g["co"], g["Np"], g["Kp"], g["Cp"], g["cin"], g["ldg"]
                 Mi = B * Hc * Wc
                 cw, gw = f"cnn.cnn.conv{i}.weight", f"cnn.cnn.cg{i}.linear.weight"
-                bplan = self._plan(("b", Np), self.P(f"cnn.cnn.conv{i}.bias").shape, dev, None)
+                bplan = self._plan(("b", Np), self.P(f"cnn.cnn.cg{i}.linear.bias").shape, dev, None)
                 # the gradient images hold the first ldg of the weight images' Np rows (64 for the 16 / 32 / 64-filter layers: the bf16
                 # gradient operands are 64 columns wide there, round 4); the plans are read up to row ldg
-                for slot, master, plan, k in ((("gate", i), gw, self._plan(("gate", Np, Cp), self.P(gw).shape, dev, None), Cp),
-                                              (("conv", i), cw, self._plan(("conv", Np, Kp), self.P(cw).shape, dev, None), Kp)):
-                    tn = self._dw_swapped_tn(Mi, ldg, k)      # image element (i, j) of [ldg, k] sits at i k + j (TN) or j ldg + i
-                    items.append(("cnn", slot, ldg * k, master, plan, ldg * k, k, k if tn else 1, 1 if tn else ldg))
+                # (dynamic layer: the convolution's image has the 4 co rows of the basis kernels, ldg4 of them in the gradient image)
+                Nc, ldc = (g["Nc"], g["ldg4"]) if g["dyn"] else (Np, ldg)
+                for slot, master, plan, k, rows_ in ((("gate", i), gw, self._plan(("gate", Np, Cp), self.P(gw).shape, dev, None), Cp, ldg),
+                                                     (("conv", i), cw, self._plan(("conv", Nc, Kp), self.P(cw).shape, dev, None), Kp, ldc)):
+                    tn = self._dw_swapped_tn(Mi, rows_, k)      # image element (i, j) of [rows, k] sits at i k + j (TN) or j rows + i
+                    items.append(("cnn", slot, rows_ * k, master, plan, rows_ * k, k, k if tn else 1, 1 if tn else rows_))
                 items += [("cnn", ("gate_b", i), ldg, f"cnn.cnn.cg{i}.linear.bias", bplan, ldg, ldg, 0, 1),
-                          ("cnn", ("conv_b", i), ldg, f"cnn.cnn.conv{i}.bias", bplan, ldg, ldg, 0, 1),
+                          # (the column sums of a (x) dY that the weight-gradient GEMM also writes have no master in a dynamic layer)
+                          ("cnn", ("conv_b", i), ldc, None if g["dyn"] else f"cnn.cnn.conv{i}.bias", None if g["dyn"] else bplan, ldc, ldc, 0, 1),
                           ("cnn", ("bn_s1", i), co, f"cnn.cnn.batchnorm{i}.bias", None, co, co, 0, 1),
                           ("cnn", ("bn_s2", i), co, f"cnn.cnn.batchnorm{i}.weight", None, co, co, 0, 1)]
                 ph, pw = m.cnn_pooling[i]
                 Hc, Wc = Hc // ph, Wc // pw
         if not items:
             return {}, {}
-        gp = lambda n: G(n).data_ptr() if G(n) is not None else 0      # (a master without a gradient slot: its image is formed and dropped)
-        key = (B, str(dev), dec_train, cnn_train, tuple(gp(it[3]) for it in items))
+        gp = lambda n: G(n).data_ptr() if (n is not None and G(n) is not None) else 0      # (a master without a gradient slot: its image is formed and dropped)
+        key = (B, T, str(dev), dec_train, cnn_train, tuple(gp(it[3]) for it in items))
         if getattr(self, "_gslot_key", None) != key:
             total = sum((it[2] + 63) // 64 * 64 for it in items)
             arena = torch.empty(total, dtype=F32, device=dev)
@@ -722,12 +792,16 @@ class PmamEngine(SedEngine):
             dY16 = E(Mi, ldyo, dt=BF16)
             call("sed_bn_bwd", dz, ldy, L["Y"], ldy, L["ah"], L["bh"], self.P(bn + "weight"), s1, s2, dY16, ldyo, Mi, co)
             del dz, dL16
-            if L["col"] is None:      # direct first convolution: the patches come from the spectrogram again; [ldg, Kp] image as the TN kernel's
+            if aux["dyn"]:
+                pass              # (the weight gradient of the four basis kernels takes a (x) dY: `_fdy_mix_bwd` below)
+            elif L["col"] is None:      # direct first convolution: the patches come from the spectrogram again; [ldg, Kp] image as the TN kernel's
                 call("sed_conv0_dw16", dY16, ldyo, L["mel"], slots[("conv", i)], Kp, slots[("conv_b", i)], B, Hc)
             else:
                 self._dw_swapped(dY16, L["col"], Mi, co, 9 * cin, out=(slots[("conv", i)], slots[("conv_b", i)]), n_img=ldg)
             cv = f"cnn.cnn.conv{i}."
-            if i > 0:
+            if aux["dyn"]:
+                dout = self._fdy_mix_bwd(W, i, aux, L, dY16, B, G, slots)
+            elif i > 0:
                 dcol = E(Mi, Kp, dt=BF16)
                 gemm_nt(dY16, W[cv + "weight"].wt, EPI_BF16, outH=dcol, K=ldg)      # (the first ldg of the transposed image's Np columns)
                 dout = E(B, Hc, Wc, cin)

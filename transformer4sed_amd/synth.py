@@ -353,6 +353,46 @@ def pmam_state_dict_np(tag="pmam0", **kw):
 
 
 # --------------------------------------------------------------------------------------------------
+# `PaSST_CNN` with the frequency-dynamic CNN branch (cnn_name "FDY-CNN"; src/models/cnn/FDY_cnn.py:7-32,66-93,119-173)
+# --------------------------------------------------------------------------------------------------
+FDY_FILTERS = (16, 32, 64, 128, 128, 128, 128)          # the canonical FDY-CRNN stack (FDY_cnn.py:127-131 defaults widened to 7 layers)
+FDY_POOLING = ((2, 2), (2, 2), (1, 2), (1, 2), (1, 2), (1, 2), (1, 2))
+FDY_DY_LAYERS = (0, 1, 1, 1, 1, 1, 1)
+FDY_TAP_GAIN = 64.0      # on attention.conv1d1.weight: the frequency-pooled activations are small (|.| ~ 0.1)
+FDY_ATT_GAIN = 25.0       # on attention.conv1d2.weight: with the reference's own initialisation every attention weight stays within 0.246-0.254
+
+
+def fdy_cnn_state_dict_np(tag="fdy0", nb_filters=FDY_FILTERS, dy_layers=FDY_DY_LAYERS, att_gain=FDY_ATT_GAIN, **kw):
+    """`pmam_state_dict_np` with the dynamic layers' tensors in place of their static ones: `conv{i}.weight` [4, co, ci, 3, 3] (four
+    different basis kernels), no `conv{i}.bias`, and the attention head -- conv1d1 at unit gain, a non-trivial BatchNorm1d affine with
+    running statistics away from (0, 1), and conv1d2 with `att_gain` so that softmax(. / 31) really selects between the kernels."""
+    base = pmam_state_dict_np(tag=tag, nb_filters=tuple(nb_filters), **kw)
+    out = {}
+    cin = {i: (1 if i == 0 else nb_filters[i - 1]) for i in range(len(nb_filters))}
+    for name, w in base.items():
+        mt = name.startswith("cnn.cnn.conv") and int(name.split(".")[2][4:])
+        if name.startswith("cnn.cnn.conv") and dy_layers[mt]:
+            if name.endswith(".bias"):
+                continue
+            i, ci, co = mt, cin[mt], nb_filters[mt]
+            hid = max(ci // 4, 4)
+            pre = f"cnn.cnn.conv{i}."
+            key = f"{tag}/{pre}"
+            out[pre + "weight"] = (det_uniform(key + "weight5", (4, co, ci, 3, 3)) * (1.4 * math.sqrt(3.0 / (9 * ci)))).astype(np.float32)
+            out[pre + "attention.conv1d1.weight"] = (det_uniform(key + "c1", (hid, ci, 3)) * (FDY_TAP_GAIN * math.sqrt(3.0 / (3 * ci)))).astype(np.float32)
+            out[pre + "attention.bn.weight"] = (1.0 + 0.2 * det_uniform(key + "bnw", (hid,))).astype(np.float32)
+            out[pre + "attention.bn.bias"] = (0.1 * det_uniform(key + "bnb", (hid,))).astype(np.float32)
+            out[pre + "attention.bn.running_mean"] = (0.3 * det_uniform(key + "bnm", (hid,))).astype(np.float32)
+            out[pre + "attention.bn.running_var"] = (1.0 + 0.5 * det_uniform(key + "bnv", (hid,))).astype(np.float32)
+            out[pre + "attention.bn.num_batches_tracked"] = np.asarray(3, dtype=np.int64)
+            out[pre + "attention.conv1d2.weight"] = (det_uniform(key + "c2", (4, hid, 1)) * (att_gain * math.sqrt(3.0 / hid))).astype(np.float32)
+            out[pre + "attention.conv1d2.bias"] = (0.1 * det_uniform(key + "c2b", (4,))).astype(np.float32)
+            continue
+        out[name] = w
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # DASM (open-vocabulary model, BASELINE.json config #5) state_dict -- names / shapes of src/models/detect_any_sound/detect_any_sound.py:
 # 69-78 (joint layers), 80-125 (SED decoder, sed_head, mask_embedding_layer), 127-171 (query projector, learnable / external queries),
 # 173-188 (at_decoder = nn.TransformerDecoder of CrossAttentionFirstDecoderLayer, at_adapter.py:36-45; at_head); the backbone, CNN
