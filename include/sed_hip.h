@@ -360,6 +360,19 @@ int sed_attnpool_bwd(const void* kv, const float* q, const float* probs, const f
 int sed_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float wd, float beta1,
                   float beta2, float eps, int step, float ema_alpha, int do_adam, hipStream_t stream);
 
+/* ---- gradient-norm clipping on the flat fp32 gradient arena (csrc/grad_clip.hip): torch.nn.utils.clip_grad_norm_ with norm_type 2 as
+ * three launches without a host synchronisation.  Every sum runs in a fixed order (no float atomics): results are bit-reproducible. */
+/* partial[c] = sum of g[i]^2 over chunk c; chunk_tab int32 [n_chunks, 2] = {arena offset (multiple of 4), length in floats}: a chunk lies
+ * inside one tensor's slice (at most 16384 floats from the host table, transformer4sed_amd/grad_clip.py); fp32, one workgroup per chunk */
+int sed_grad_sumsq_chunks(const float* g, const int32_t* chunk_tab, int n_chunks, float* partial, hipStream_t stream);
+/* tensor_first_chunk int32 [n_tensors + 1] (tensor t owns chunks [first[t], first[t + 1]), possibly none).  fp64 sums in chunk, then layout
+ * order: norms[t] = sqrt(sumsq_t), total_and_scale = {total = sqrt(sum_t sumsq_t), scale = min(1, max_norm / (total + 1e-6))} (torch's
+ * clip coefficient, non-finite values not special-cased: error_if_nonfinite=False); max_norm <= 0: measure only, scale = 1 */
+int sed_grad_norm_finalize(const float* partial, const int32_t* tensor_first_chunk, int n_tensors, float max_norm,
+                           float* norms /*[n_tensors]*/, float* total_and_scale /*[2]*/, hipStream_t stream);
+/* g[0..n) *= scale[0] (device scalar; n a multiple of 4).  scale >= 1: returns without reading or writing g */
+int sed_scale_by_dev(float* g, int64_t n, const float* scale, hipStream_t stream);
+
 /* every weight image of a model in one launch (what sed_transpose_to_bf16 + sed_split3_f16 produce per weight): desc is a device
  * table of n_desc x 16 int64 {fp32 master, transposed bf16 image [C, R] or 0, straight 16-bit image [R, C] or 0,
  * split-precision f16 image [R, 3C] = [hi | hi | lo] or 0, R (multiple of 16), C (multiple of 64), straight-image kind

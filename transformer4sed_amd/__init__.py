@@ -7,3 +7,5 @@ and RCCL adds its streams once a process group exists -- with 4 queues the teach
 two passes serialise (measured at world size 1 with the RCCL path forced on: +2.4 % -> +0.7 % per step with 8 queues,
 profiles/r5_host_contention.txt).  `transformer4sed_amd.hostcpu.recommended_env()` returns it for launch scripts; until round 5 the package
 set it as an import side effect."""
+
+from .grad_clip import clip_grad_norm_, grad_chunk_table, grad_norms  # noqa: E402,F401  (host arithmetic + lazy imports: loads no library)

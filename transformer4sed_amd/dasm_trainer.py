@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import data_aug
+from .grad_clip import clip_grad_norm_, max_grad_norm_of
 from .ops import call
 from .trainer import pool_strong_labels
 
@@ -93,6 +94,7 @@ class AudiosetStrongTrainer:
     def __init__(self, net, optimizer, scheduler, config, sr=16000, ddp=None):
         self.net, self.optimizer, self.scheduler, self.config, self.sr, self.ddp = net, optimizer, scheduler, config, sr, ddp
         self.supervised_loss = loss_function_factory(config["class_loss"]["loss_name"], config["class_loss"].get("kwargs"))
+        self.max_grad_norm = max_grad_norm_of(config.get("training") or {})     # optional; not the reference's `clip_grad` (see `_finish`)
         from .hostcpu import cap_torch_threads
         cap_torch_threads()
 
@@ -123,9 +125,14 @@ class AudiosetStrongTrainer:
         self._after_backward()
         if self.ddp is not None:
             self.ddp.allreduce_grads(self.net)
+        out = {k: v.detach() for k, v in terms.items()}
+        if self.max_grad_norm is not None:
+            # training["max_grad_norm"] (grad_clip.py): the arena is final here -- `_after_backward` has moved the open-vocabulary queries'
+            # gradient into it and the all-reduce has run.  The gradient of an external query INPUT is no parameter's and is not clipped
+            out["grad_norm"] = clip_grad_norm_(self.net, self.max_grad_norm)
         self.optimizer.step(None)
         self.scheduler.step()
-        return {k: v.detach() for k, v in terms.items()}
+        return out
 
     def _after_backward(self):
         pass

@@ -254,10 +254,13 @@ def _hbm_bytes_of(name, args):
     if name == "sed_layernorm_bwd_x16":          # (..., dbeta, dx16, M, D): + the bf16 image
         M, D = args[11], args[12]
         return float(M) * (D * (14 + (4 if args[7] else 0)) + 8)
+    if name == "sed_scale_by_dev":               # (g, n, scale): read + write when the scale is below 1 (nothing otherwise: not known here;
+        #  sed_grad_sumsq_chunks reads the arena once, 4 B per element -- its arguments do not say how many: tools/grad_clip_bench.py counts them)
+        return 8.0 * args[1]
     return 0.0
 
 
-HBM_KERNELS = ("sed_logmel_fwd", "sed_adamw_ema", "sed_layernorm_fwd", "sed_layernorm_bwd", "sed_layernorm_bwd_x16")
+HBM_KERNELS = ("sed_logmel_fwd", "sed_adamw_ema", "sed_layernorm_fwd", "sed_layernorm_bwd", "sed_layernorm_bwd_x16", "sed_scale_by_dev")
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # the current stream's handle without building a Stream object
 

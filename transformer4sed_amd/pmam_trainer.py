@@ -7,6 +7,7 @@ import re
 import torch
 
 from . import data_aug
+from .grad_clip import clip_grad_norm_, max_grad_norm_of
 from .ops import call
 
 
@@ -110,6 +111,7 @@ class PmamTrainer:
         self.net, self.optimizer, self.scheduler, self.cfg, self.net_pooling, self.ddp = net, optimizer, scheduler, config, net_pooling, ddp
         self.protos = torch.nn.functional.normalize(gmm_means.float(), dim=-1).to(next(net.parameters()).device)   # train.py:31
         self.bce = torch.nn.BCELoss()
+        self.max_grad_norm = max_grad_norm_of(config.get("training") or {})     # optional; `clip_grad` keeps the reference's no-op (see `step`)
         from .hostcpu import cap_torch_threads
         cap_torch_threads()     # training entry point: see hostcpu.py (SED_HOST_THREADS=0 opts out)
 
@@ -154,8 +156,10 @@ class PmamTrainer:
         loss_total.backward()
         if self.ddp is not None:
             self.ddp.allreduce_grads(self.net)
+        # training["max_grad_norm"] (grad_clip.py): a clip of the gradients this backward produced, identical on every rank after the all-reduce
+        gn = {} if self.max_grad_norm is None else {"grad_norm": clip_grad_norm_(self.net, self.max_grad_norm)}
         self.optimizer.step(None)
         self.optimizer.zero_grad()
         self.scheduler.step()
         return dict(loss_total=loss_total.detach(), loss_strong=loss_strong.detach(),
-                    loss_weak=loss_weak.detach() if torch.is_tensor(loss_weak) else loss_weak)
+                    loss_weak=loss_weak.detach() if torch.is_tensor(loss_weak) else loss_weak, **gn)

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import data_aug
+from .grad_clip import clip_grad_norm_, max_grad_norm_of
 from .ops import call
 from .scheduler import cons_weight, ema_alpha
 
@@ -198,6 +199,11 @@ class FusedAdamWEMA:
                 cur = None
         return runs
 
+    def clip_grad_norm_(self, max_norm, norm_type=2.0):
+        """`grad_clip.clip_grad_norm_` on the bound model's gradient arena, to call between backward() and step(): scales the gradients
+        in place, returns their total norm before clipping (device tensor)."""
+        return clip_grad_norm_(self.net, max_norm, norm_type)
+
     def step(self, ema_alpha_value=None):
         """One AdamW step on every parameter that has a gradient (torch skips grad-less params, so do we), then
         ema = alpha * ema + (1 - alpha) * p over ALL parameters when `ema_alpha_value` is given."""
@@ -298,6 +304,9 @@ class MatSedTrainer:
         self.epoch_len = epoch_len
         self.net_pooling = net_pooling
         self.ddp = ddp
+        # optional training["max_grad_norm"]: a clip that works, AFTER backward (grad_clip.py).  The reference's `clip_grad` key is not it: it
+        # clips before backward (quirk 4) and stays the no-op it is there
+        self.max_grad_norm = max_grad_norm_of(config.get("training") or {})
         self.bce = torch.nn.BCELoss()
         self.mse = torch.nn.MSELoss()
         import os
@@ -433,6 +442,13 @@ class MatSedTrainer:
         label_weak[:strong_n] = pool_strong_labels(label[:strong_n])
         return stu_mel, tch_mel, label, label_weak
 
+    def _clip(self):
+        """With training["max_grad_norm"] set: clip the (all-reduced: every rank holds the same averaged gradients, so no further
+        collective) gradient arena, -> {"grad_norm": total norm before clipping, device tensor}.  Unset: nothing is launched, -> {}."""
+        if self.max_grad_norm is None:
+            return {}
+        return {"grad_norm": clip_grad_norm_(self.net, self.max_grad_norm)}
+
     def finetune_step(self, wav, labels):
         """One mean-teacher step (train.py:143-208).  Returns the dict of scalar losses (device tensors; no host sync)."""
         tr = self.cfg["training"]
@@ -474,10 +490,11 @@ class MatSedTrainer:
             loss_total.backward()
             if self.ddp is not None:
                 self.ddp.allreduce_grads(self.net)
+            gn = self._clip()
             self.optimizer.step(ema_alpha(self.scheduler.step_num + 1, tr["ema_factor"]))
             self.scheduler.step()
             return dict(loss_total=loss_total.detach(), loss_class_strong=terms[1], loss_class_weak=terms[2], loss_class_at_specific=terms[3],
-                        loss_cons_strong=terms[4], loss_cons_weak=terms[5], loss_cons_at_specific=terms[6], w_cons=w_cons)
+                        loss_cons_strong=terms[4], loss_cons_weak=terms[5], loss_cons_at_specific=terms[6], w_cons=w_cons, **gn)
         l_at = self.bce(at_s[ws], labels_weak[ws])
         lc_at = self.mse(at_s, at_t)
         l_strong = self.bce(stu_strong[:strong_n], labels[:strong_n])
@@ -489,13 +506,14 @@ class MatSedTrainer:
         loss_total.backward()  # (the reference's clip_grad_norm before backward is a no-op)
         if self.ddp is not None:
             self.ddp.allreduce_grads(self.net)
+        gn = self._clip()
         # reference order (train.py:197-201): optimizer.step() with the current lr, scheduler.step(), then update_ema with
         # the already incremented step_num -> alpha = min(1 - 1/(step_num + 1), ema_factor) fused into the same sweep
         self.optimizer.step(ema_alpha(self.scheduler.step_num + 1, tr["ema_factor"]))
         self.scheduler.step()
         return dict(loss_total=loss_total.detach(), loss_class_strong=l_strong.detach(), loss_class_weak=l_weak.detach(),
                     loss_class_at_specific=l_at.detach(), loss_cons_strong=lc_strong.detach(),
-                    loss_cons_weak=lc_weak.detach(), loss_cons_at_specific=lc_at.detach(), w_cons=w_cons)
+                    loss_cons_weak=lc_weak.detach(), loss_cons_at_specific=lc_at.detach(), w_cons=w_cons, **gn)
 
     def pretrain_step(self, wav):
         """One masked-reconstruction step (mlm_passt/train.py:23-45)."""
@@ -509,7 +527,8 @@ class MatSedTrainer:
         loss.backward()
         if self.ddp is not None:
             self.ddp.allreduce_grads(self.net)
+        gn = self._clip()
         self.optimizer.step(None)
         self.optimizer.zero_grad()
         self.scheduler.step()
-        return dict(loss=loss.detach())
+        return dict(loss=loss.detach(), **gn)
