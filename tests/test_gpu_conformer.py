@@ -9,14 +9,12 @@ f16 (between 2^-9 and 2^-8, 2^-12 and 2^-11 of |x|: what a correctly rounded sto
 
 Model level: the depth-2 synth-weight model against the reference goldens of tools/gen_conformer_golden.py, with the bounds of
 tests/test_gpu_band_attention.py (posteriors within 1e-3: the project's contract)."""
-import functools
 import os
 from copy import deepcopy
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
@@ -24,27 +22,15 @@ from transformer4sed_amd import synth  # noqa: E402
 from transformer4sed_amd.ops import call, BF16, F16  # noqa: E402
 from transformer4sed_amd.passt_sed import PaSST_SED  # noqa: E402
 
+# the pure-torch half of this file (the restatement, its inputs and references, the storage term of the bound) lives in tests/walk_cases.py,
+# where tests/test_walk_cases_cpu.py can import it without a GPU
+from walk_cases import C, KW, SIG_BITS, chain, half_ulp, inputs, maxerr, reference  # noqa: E402,F401
+
 DEV = "cuda"
-C, KW = 768, 31
 LOGDIR = os.environ.get("SED_TEST_LOG_DIR") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "test_logs")
 LOG = os.path.join(LOGDIR, "conformer_kernel_errors.log")
 MLOG = os.path.join(LOGDIR, "conformer_model_errors.log")
 SHAPES = [(1, 8), (3, 31), (2, 65), (3, 100), (2, 1000)]
-SIG_BITS = {"bf16": 8, "f16": 11}       # significand bits (with the hidden one) of the 16-bit storage formats
-
-
-def maxerr(a, b):
-    return float((a.detach().double().cpu() - b.detach().double().cpu()).abs().max())
-
-
-def half_ulp(ref64, storage):
-    """Half a unit in the last place of `storage` at each element's magnitude: 2^(floor(log2 |x|) - p) for p significand bits (between
-    2^-(p+1) and 2^-p of |x|; f16 subnormals: 2^-25).  Zero for fp32 outputs."""
-    if storage == "f32":
-        return torch.zeros_like(ref64)
-    _, e = torch.frexp(ref64.abs().clamp_min(1e-300))          # |x| = m 2^e, 0.5 <= m < 1
-    h = torch.ldexp(torch.ones_like(ref64), e - 1 - SIG_BITS[storage])
-    return h.clamp_min(2.0 ** -25) if storage == "f16" else h
 
 
 def check(name, got, ref64, ref32, storage="f32"):
@@ -59,42 +45,6 @@ def check(name, got, ref64, ref32, storage="f32"):
                 f"worst_err_over_bound={worst:.3f}\n")
     print(f"{name}: err {err:.3e} yardstick {yard:.3e} worst err / bound {worst:.3f}")
     assert bool((diff <= tol).all()), (name, err, yard, worst)
-
-
-# ------------------------------------------------------------------------------------------------ the restatement
-def chain(x, w, b, gamma, beta, B, T, conv=True):
-    """x [B T, 2 C] -> (y [B T, C], c [B T, C]) in x's dtype."""
-    u = F.glu(x.view(B, T, 2 * C).transpose(1, 2), dim=1)
-    c = F.conv1d(u, w.view(C, 1, KW), b, padding=KW // 2, groups=C) if conv else u
-    c = c.transpose(1, 2)
-    n = F.layer_norm(c, (C,), gamma, beta, 1e-5)
-    return (n * torch.sigmoid(n)).reshape(B * T, C), c.reshape(B * T, C)
-
-
-def inputs(B, T, tag="k"):
-    """fp32 inputs (the kernel's input format: nothing to round)."""
-    M = B * T
-    return dict(x=torch.from_numpy(synth.det_normal(f"conf/{tag}/x/{B}x{T}", (M, 2 * C), 1.5)),
-                w=torch.from_numpy(0.35 * synth.det_uniform(f"conf/{tag}/w", (C, KW))),
-                b=torch.from_numpy(0.1 * synth.det_uniform(f"conf/{tag}/b", (C,))),
-                gamma=torch.from_numpy(1.0 + 0.2 * synth.det_uniform(f"conf/{tag}/g", (C,))),
-                beta=torch.from_numpy(0.1 * synth.det_uniform(f"conf/{tag}/bt", (C,))),
-                dy=torch.from_numpy(synth.det_uniform(f"conf/{tag}/dy/{B}x{T}", (M, C))))
-
-
-@functools.lru_cache(maxsize=None)
-def reference(B, T):
-    """The restatement in float64 and float32 on the CPU, forward and (autograd) backward; computed once per shape."""
-    out = {}
-    for dt in (torch.float64, torch.float32):
-        t = {k: v.to(dt).requires_grad_(k != "dy") for k, v in inputs(B, T).items()}
-        y, c = chain(t["x"], t["w"], t["b"], t["gamma"], t["beta"], B, T)
-        mu = c.mean(-1)
-        rstd = (c.var(-1, unbiased=False) + 1e-5).rsqrt()
-        (y * t["dy"]).sum().backward()
-        out[dt] = dict(y=y.detach(), c=c.detach(), mean=mu.detach(), rstd=rstd.detach(), dx=t["x"].grad, dw=t["w"].grad, db=t["b"].grad,
-                       dgamma=t["gamma"].grad, dbeta=t["beta"].grad)
-    return out[torch.float64], out[torch.float32]
 
 
 def run_fwd(t, B, T, mode=4, save=True, y32=True):

@@ -21,6 +21,7 @@ import torch
 import torch.nn.functional as F
 
 import fdy_cases as FC
+from fdy_cases import head_inputs, head_ref  # noqa: F401  (pure torch: shared with tests/walk_cases.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -121,32 +122,6 @@ def test_mix_forward_and_backward(B, H, W, co):
 
 
 # ================================================================================================ kernel level: frequency mean + attention head
-def head_inputs(B, H, W, cin, temperature):
-    hid = FC.hid_of(cin)
-    tag = f"fdy/head/{B}x{H}x{W}x{cin}"
-    u = lambda k, shp, s=1.0: torch.from_numpy(synth.det_uniform(f"{tag}/{k}", shp) * s).float()
-    return dict(x=torch.from_numpy(FC.exact16(tag + "/x", (B, H, W, cin), 2.0)),
-                c1w=u("c1", (hid, cin, 3), 3.0 / np.sqrt(3 * cin)), bn_w=1.0 + u("bnw", (hid,), 0.2), bn_b=u("bnb", (hid,), 0.1),
-                bn_rm=u("bnm", (hid,), 0.3), bn_rv=1.0 + u("bnv", (hid,), 0.5),
-                c2w=u("c2", (4, hid, 1), 2.0 * temperature / np.sqrt(hid)), c2b=u("c2b", (4,), 0.1),       # logits / temperature of a few units
-                da=torch.from_numpy(synth.det_normal(tag + "/da", (B * H, 4), 1.0)), dx0=torch.from_numpy(synth.det_normal(tag + "/dx0", (B, H, W, cin), 1.0)))
-
-
-def head_ref(inp, temperature, train, dt):
-    """-> dict of pm [R, cin], att [R, 4], batch mean / var, and through autograd of sum(att da): dX (on top of dx0), parameter gradients."""
-    t = {k: v.to(dt) for k, v in inp.items()}
-    B, H, W, cin = t["x"].shape
-    x = t["x"].permute(0, 3, 1, 2).contiguous().requires_grad_(True)
-    ps = {k: t[k].clone().requires_grad_(True) for k in ("c1w", "bn_w", "bn_b", "c2w", "c2b")}
-    pm = x.mean(3)
-    att, mean, var = FC.attention_head(pm, ps["c1w"], ps["bn_w"], ps["bn_b"], t["bn_rm"], t["bn_rv"], ps["c2w"], ps["c2b"], temperature, train)
-    (att.permute(0, 2, 1).reshape(-1, 4) * t["da"]).sum().backward()
-    out = dict(pm=pm.detach().permute(0, 2, 1).reshape(-1, cin), att=att.detach().permute(0, 2, 1).reshape(-1, 4), mean=mean.detach(), var=var.detach(),
-               dX=t["dx0"] + x.grad.permute(0, 2, 3, 1))
-    out.update({"g_" + k: v.grad for k, v in ps.items()})
-    return out
-
-
 @pytest.mark.parametrize("temperature", FC.TEMPERATURES)
 @pytest.mark.parametrize("train", [True, False])
 @pytest.mark.parametrize("B,H,W,cin", FC.HEAD_CASES)
