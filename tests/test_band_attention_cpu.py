@@ -69,6 +69,11 @@ def test_pmam_model_takes_the_window():
     net = PaSST_CNN(passt_sed_param=dict(sed, decoder_win_len=64), cnn_param=cnn)
     assert torch.equal(net.state_dict()["decoder.att_mask"], closed_form(64))
     assert "decoder.att_mask" not in PaSST_CNN(passt_sed_param=sed, cnn_param=cnn).state_dict()
+    # its engine walks the one Transformer-XL schedule (windowed or not), overriding pieces of it only
+    from transformer4sed_amd.engine import SedEngine
+    from transformer4sed_amd.pmam_engine import PmamEngine
+    assert isinstance(net._make_engine(), PmamEngine)
+    assert PmamEngine._decoder_fwd is SedEngine._decoder_fwd and PmamEngine._decoder_bwd is SedEngine._decoder_bwd
 
 
 def test_state_dict_round_trip_and_absent_key():

@@ -22,7 +22,7 @@ import numpy as np
 T = 200
 HEADS = [40, 100, 400] * 4      # per-head window: narrow, medium, >= 2 T (= no window on that head)
 CONFIGS = [("xl", B, win) for B in (2, 6) for win in (None, 100, HEADS)] + [("conformer", B, win) for B in (2, 6) for win in (None, 100)] \
-    + [("pmam", 6, win) for win in (None, 100)]
+    + [("pmam", B, win) for B in (2, 6) for win in (None, 100)]
 
 
 def tag_of(kind, B, win):
@@ -115,15 +115,13 @@ def main(out, tree):
             save(f"{tag}.out.{mode}", y)
             for li, L in enumerate(dctx["layers"]):
                 save(f"{tag}.lse.{mode}.{li}", L["lse"])
-            if kind == "pmam":
-                slots, scatter = eng._grad_slots(B, torch.device(dev, 0), grads.get, trainable, False)
-                gin = bwd(W, dctx, gout.clone(), grads.get, trainable, slots)
-                eng._join_dw()
-                if "dec" in scatter:
-                    call("sed_scatter_add_f32", *scatter["dec"])
-            else:
-                gin = bwd(W, dctx, gout.clone(), grads.get, trainable)
-                eng._join_dw()
+            scatter = {}
+            if kind == "pmam":      # (as PmamEngine._context_bwd: the padded gradient images, returned to the masters after the walk)
+                dctx["slots"], scatter = eng._grad_slots(B, torch.device(dev, 0), grads.get, trainable, False)
+            gin = bwd(W, dctx, gout.clone(), grads.get, trainable)
+            eng._join_dw()
+            if "dec" in scatter:
+                call("sed_scatter_add_f32", *scatter["dec"])
             torch.cuda.synchronize()
             save(f"{tag}.gin.{mode}", gin)
             for n, t in grads.items():

@@ -24,6 +24,10 @@ from .ops import EPI_F32, EPI_F32_RESID, EPI_BF16, EPI_GELU, EPI_DGELU, EPI_F32_
 
 D = 768
 H = 12
+# 16-bit type of the FORWARD MFMA operands (activations + weight images).  IEEE half keeps the frame posteriors within 1e-3 of the fp32
+# reference at the bf16 MFMA rate; gradient-side operands are always bf16.  (A bf16 forward misses that bound, so it is not a mode; the
+# kernels stay templated on the type -- the `f16` / `mode` arguments the host passes as constants -- and the kernel tests exercise both.)
+ACT = F16
 NCLS_MAX = 16
 FPOOL_TRANSFORMER = "frequency_wise_tranformer_encoder"     # f_pool value of the frequency-wise transformer pooling ((sic) the reference's spelling)
 FPOOL_HEADS = 4         # its blocks: 4 heads of 192 (src/models/pooling.py:24)
@@ -93,9 +97,9 @@ def rel_pos_table(T, Dm=D):
 
 def in_split_precision(fwd):
     """Decorator of a context-network forward: every GEMM of it runs on split-precision operands (3x K issued), so the whole call runs
-    inside ops.split_precision(), entered once.  An engine without `split` does not enter it."""
+    inside ops.split_precision(), entered once."""
     def run(self, *args):
-        if not self.split or getattr(self, "_in_split", False):
+        if getattr(self, "_in_split", False):
             return fwd(self, *args)
         self._in_split = True
         try:
@@ -138,14 +142,9 @@ class SedEngine:
         # padding written once stays zero and the buffers can be reused step after step instead of being re-zeroed (1.1 ms / step)
         self._zpool = {}
         self._pool_busy = False
-        # 16-bit type of the FORWARD MFMA operands (activations + weight images).  IEEE half keeps the frame posteriors within 1e-3 of the
-        # fp32 reference at the bf16 MFMA rate; gradient-side operands are always bf16.  (A bf16 forward misses that bound, so it is not a
-        # mode; the kernels stay templated on the type and the kernel tests exercise both.)
-        self.act = F16
-        # Context-network (and MLM head) GEMMs in split precision: f16 hi + f16 lo operands, three MFMA products via the
+        # The context-network (and MLM head) GEMMs always run in split precision: f16 hi + f16 lo operands, three MFMA products via the
         # concatenated reduction dim.  Their operand rounding is what limits posterior parity: with
         # it 1e-3 holds with a 10x margin, for ~4 % of step time; without it the posteriors miss 1e-3.
-        self.split = self.act == F16
         # weight gradients: TN kernel on the operands as they lie (default) or transposed copies + NT split-K kernel
         self.dw_tn = True                 # (attribute kept for tools/trajectory_probe.py's summation-order experiment; no environment switch)
         # weight-gradient (TN) GEMMs on a side stream: they depend only on dY and the saved operand, nothing in the backward chain
@@ -190,7 +189,7 @@ class SedEngine:
 
     def _wcorr_on(self, save):
         """Does this pass run the evaluation-mode encoder weights?"""
-        if self.act != F16 or save:
+        if save:
             return False
         if getattr(self.m, "lora_r", 0) and not getattr(self.m, "lora_merged", False):
             return False        # PaSST_CNN in train mode: the GEMM operand is W + s B A, not the master the residual image is taken from
@@ -199,7 +198,7 @@ class SedEngine:
     def _fpool_split_on(self, save):
         """Does this pass run the transformer pooling's GEMMs in split precision?  Scored passes do (module in eval mode, nothing saved);
         training-mode passes run them on plain f16 operands like the encoder blocks."""
-        return self.split and self._wcorr_on(save)
+        return self._wcorr_on(save)
 
     def _lnf_image(self, W, wname, bname, gname, btname):
         """(f16(gamma (.) W), colS, colC) of a Linear that follows a LayerNorm (sed_ln_fold_weight), cached per weight on all four
@@ -298,7 +297,7 @@ class SedEngine:
                 p = f"f_pool_module.frequency_transformer.{i}."
                 names += [p + "attn.qkv.weight", p + "attn.proj.weight", p + "mlp.fc1.weight", p + "mlp.fc2.weight"]
         fp_split = self._fpool_split_on(need_t)         # (`need_t` is the forward's `save`)
-        ptrs = tuple(self.P(n).data_ptr() for n in names) + (bool(need_t), self.split, fp_split)
+        ptrs = tuple(self.P(n).data_ptr() for n in names) + (bool(need_t), fp_split)
         if getattr(self, "_wimg_key", None) != ptrs:
             # descriptor table of sed_weight_images: rebuilt only when a master moved (optimizer arenas, .to(device))
             rows, tiles = [], 0
@@ -310,14 +309,14 @@ class SedEngine:
                     raise RuntimeError(f"weight {n}: unsupported shape / layout for the operand images")
                 ent = self.cache.get(n)
                 if ent is None or ent.w.device != w32.device:
-                    ent = _W(torch.empty(n_out, k_in, dtype=self.act, device=w32.device),
+                    ent = _W(torch.empty(n_out, k_in, dtype=ACT, device=w32.device),
                              torch.empty(k_in, n_out, dtype=BF16, device=w32.device))
                     self.cache[n] = ent
-                want_split = self.split and (n.startswith(("decoder.", "mlm_mlp")) or (fp_split and n.startswith("f_pool_module.")))
+                want_split = n.startswith(("decoder.", "mlm_mlp")) or (fp_split and n.startswith("f_pool_module."))
                 if want_split and (ent.ws is None or ent.ws.device != w32.device):
                     ent.ws = torch.empty(n_out, 3 * k_in, dtype=F16, device=w32.device)
                 rows.append([w32.data_ptr(), ent.wt.data_ptr() if need_t else 0, ent.w.data_ptr(), ent.ws.data_ptr() if want_split else 0,
-                             n_out, k_in, 2 if self.act == F16 else 0, tiles, 0, 0, 0, 0, 0, 0, 0, 0])   # (no gather plan, no LoRA term)
+                             n_out, k_in, 2, tiles, 0, 0, 0, 0, 0, 0, 0, 0])   # (no gather plan, no LoRA term)
                 tiles += ((n_out + 63) // 64) * (k_in // 64)
             self._wimg_desc = h2d(rows, torch.int64, self.P(names[0]).device)
             self._wimg_n, self._wimg_tiles, self._wimg_key = len(rows), tiles, ptrs
@@ -332,14 +331,14 @@ class SedEngine:
             tab = torch.zeros(Rpad, Dm)
             tab[:R] = rel_pos_table(T, Dm)
             tab = tab.to(dev)
-            pos16 = tab.to(self.act).contiguous()
+            pos16 = tab.to(ACT).contiguous()
             posT16 = torch.empty(Dm, Rpad, dtype=BF16, device=dev)
             transpose_bf16(tab, Rpad, Dm, posT16)
-            pos16s = split3(tab, Rpad, Dm) if self.split else None
+            pos16s = split3(tab, Rpad, Dm)
             self.pos_cache[key] = (pos16, posT16, Rpad, pos16s)
         ent = self.pos_cache[key]
         # (pos16: split image [hi | lo | hi] when the split-precision linear_pos GEMM reads it, the plain f16 table for `dec_terms2`)
-        return (ent[3] if (self.split and not (self.dec_terms2 and want_plain)) else ent[0]), ent[1], ent[2]
+        return (ent[0] if (self.dec_terms2 and want_plain) else ent[3]), ent[1], ent[2]
 
     # ------------------------------------------------------------------ encoder
     def _encoder_fwd(self, W, mel, tstarts, tp, toffsets, save, want_frame, rows=None, F=12):
@@ -356,14 +355,12 @@ class SedEngine:
         Npad = pad64(N)
         M = Bx * N
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        A16 = self.act
-        f16 = 1 if A16 == F16 else 0
         rows = [None] * nS if rows is None else rows
         ctx = dict(B=Bx, N=N, Npad=Npad, tp=tp, layers=[], toffsets=toffsets, nS=nS, F=F, rows=rows)
         Ms = B * F * tp             # patch rows of one slab
-        cols = E(nS * Ms, 256, dt=A16)
+        cols = E(nS * Ms, 256, dt=ACT)
         for s, ts in enumerate(tstarts):
-            call("sed_im2col_rows", mel, cols[s * Ms:(s + 1) * Ms], rows[s], F, B, T, ts, tp, f16)
+            call("sed_im2col_rows", mel, cols[s * Ms:(s + 1) * Ms], rows[s], F, B, T, ts, tp, 1)
         conv = E(nS * Ms, D)
         gemm_nt(cols, W["backbone.patch_embed.proj.weight"].w, EPI_F32, bias=self.P("backbone.patch_embed.proj.bias"),
                 outF=conv)
@@ -381,7 +378,7 @@ class SedEngine:
         lo_f = self._lowest_trainable_fwd(m.depth) if save else m.depth
         # q, k, v stay row-major: the attention forward and backward take every transposed operand out of their LDS tiles
         # (ds_read_b64_tr_b16); the backward makes the bf16 images of the saved f16 Q / K / V tiles on the way into LDS
-        mk_qkv = lambda: [E(Bx * H, N, 64, dt=A16), E(Bx * H, N, 64, dt=A16), E(Bx * H, N, 64, dt=A16)]
+        mk_qkv = lambda: [E(Bx * H, N, 64, dt=ACT), E(Bx * H, N, 64, dt=ACT), E(Bx * H, N, 64, dt=ACT)]
         scratch = None          # per-call scratch (reused across layers when not saving)
         pooled = None
         # Form of each linear site in this pass (the constructor's comment on the evaluation-mode encoder): "f16" plain weights (training,
@@ -418,7 +415,7 @@ class SedEngine:
         # it -- the residual GEMM writes the f16 image of the new stream + per-row partial sums, the next GEMM consumes the RAW image against
         # gamma-scaled weights and normalises in its epilogue (csrc/gemm.hip, GemmArgs.rowpart / rowstat).  Two passes over the stream less
         # per block.  SED_LN_FOLD=0 keeps the LayerNorm kernels.
-        fold_ok = self.ln_fold and not wc and self.act == F16 and M >= 1024 and not getattr(m, "lora_r", 0) and (not save or lo_f > 0)
+        fold_ok = self.ln_fold and not wc and M >= 1024 and not getattr(m, "lora_r", 0) and (not save or lo_f > 0)
         have_stat = False       # statistics of the current stream available (false before the first residual GEMM)
         if fold_ok:
             # between folded blocks the residual stream lives as two planes (x16f = f16 hi, which is also the consumers' A operand, + xlo:
@@ -435,29 +432,29 @@ class SedEngine:
             sv = save and li >= lo_f          # this block's activations are read by a backward
             fold = fold_ok and not sv
             if sv or scratch is None:
-                h16 = E(M, pitch(q8), dt=A16)
+                h16 = E(M, pitch(q8), dt=ACT)
                 q, k, v = mk_qkv()
-                o16 = E(M, pitch(p8), dt=A16)
+                o16 = E(M, pitch(p8), dt=ACT)
                 lse = E(Bx * H, N)
-                h2 = E(M, D, dt=A16)
+                h2 = E(M, D, dt=ACT)
                 hpre = E(M, 4 * D, dt=BF16) if sv else None       # (GELU pre-activation: only the backward reads it, so bf16 right away)
-                act = E(M, 4 * pitch(f28), dt=A16)
+                act = E(M, 4 * pitch(f28), dt=ACT)
                 mean1, rstd1, mean2, rstd2 = (E(M), E(M), E(M), E(M)) if sv else (None, None, None, None)
                 scratch = (h16, q, k, v, o16, lse, h2, hpre, act)
             else:
                 h16, q, k, v, o16, lse, h2, hpre, act = scratch
                 mean1 = rstd1 = mean2 = rstd2 = None
             x_in = x
-            # Saving blocks of an f16 pass: the LayerNorm writes its result twice -- f16 for the forward GEMM, bf16 for the backward's weight
+            # Saving blocks: the LayerNorm writes its result twice -- f16 for the forward GEMM, bf16 for the backward's weight
             # gradient, which otherwise converts the saved f16 fragments in registers (17-20 % of that launch).  The f16 tensors are not kept.
-            dual = sv and f16 == 1 and not getattr(m, "lora_r", 0)      # (LoRA factors take their gradients from the f16 operand)
+            dual = sv and not getattr(m, "lora_r", 0)      # (LoRA factors take their gradients from the f16 operand)
             h16s = h2s = None
             if dual:
                 h16s, h2s = E(M, D, dt=BF16), E(M, D, dt=BF16)
                 call("sed_layernorm_fwd_dual", x_in, self.P(p + "norm1.weight"), self.P(p + "norm1.bias"), 1e-6, 1.0, h16, h16s, mean1, rstd1, M, D)
             elif not (fold and have_stat):
                 call("sed_layernorm_fwd", x_in, self.P(p + "norm1.weight"), self.P(p + "norm1.bias"), 1e-6, 1.0, h16, None,
-                     mean1, rstd1, M, D, 8 if q8 else f16)
+                     mean1, rstd1, M, D, 8 if q8 else 1)
             wq, bq = p + "attn.qkv.weight", self.P(p + "attn.qkv.bias")
             if fold:
                 last = li + 1 == m.depth or (li + 1 == m.passt_feature_layer and not want_frame) or (save and li + 1 >= lo_f)
@@ -465,9 +462,9 @@ class SedEngine:
                     wf, sq, cq = self._lnf_image(W, wq, p + "attn.qkv.bias", p + "norm1.weight", p + "norm1.bias")
                     call(qkv_lnc, x16f, wf, cq, sq, statf, M, D, H, N, Npad, q, k, v)
                 else:       # first block: its LayerNorm ran above (the stream comes from the token assembly, not from a GEMM)
-                    call("sed_gemm_qkv", h16, W[wq].w, bq, M, D, H, N, Npad, q, k, v, None, None, None, None, None, None, None, f16)
+                    call("sed_gemm_qkv", h16, W[wq].w, bq, M, D, H, N, Npad, q, k, v, None, None, None, None, None, None, None, 1)
                 # (byte-plane runs: the attention output goes head-major = slab-major into the proj GEMM's A operand)
-                call("sed_mhsa_fwd", q, k, v, o16, lse, Bx, H, N, Npad, f16 | (2 if lo8 else 0))
+                call("sed_mhsa_fwd", q, k, v, o16, lse, Bx, H, N, Npad, 1 | (2 if lo8 else 0))
                 call(lnp, o16, W[p + "attn.proj.weight"].w, M, D, D, 64 if lo8 else D, D, self.P(p + "attn.proj.bias"),
                      None if planes else x_in, x16f if planes else None, xlo if planes else None, None, x16f, xlo, partf, D)
                 call("sed_ln_fold_stats", partf, statf, M, D // 64, D, 1e-6)
@@ -489,19 +486,19 @@ class SedEngine:
                     img, s = self._w2f8_image(W, wq)
                     call("sed_gemm_qkv_w2f8", h16, img, bq, M, D, H, N, Npad, q, k, v, s)
                 elif f_qkv == "w2":
-                    call("sed_gemm_qkv_w2", h16, self._w2_image(W, wq), bq, M, D, H, N, Npad, q, k, v, f16)
+                    call("sed_gemm_qkv_w2", h16, self._w2_image(W, wq), bq, M, D, H, N, Npad, q, k, v, 1)
                 elif f_qkv == "gb":
-                    call("sed_gemm_qkv_gb", h16, W[wq].w, bq, M, D, H, N, Npad, q, k, v, f16, self._wcorr_bias(W, wq, h16, Bx, N), N)
+                    call("sed_gemm_qkv_gb", h16, W[wq].w, bq, M, D, H, N, Npad, q, k, v, 1, self._wcorr_bias(W, wq, h16, Bx, N), N)
                 else:
-                    call("sed_gemm_qkv", h16, W[wq].w, bq, M, D, H, N, Npad, q, k, v, None, None, None, None, None, None, None, f16)
-                call("sed_mhsa_fwd", q, k, v, o16, lse, Bx, H, N, Npad, f16 | (4 if p8 else 0))
+                    call("sed_gemm_qkv", h16, W[wq].w, bq, M, D, H, N, Npad, q, k, v, None, None, None, None, None, None, None, 1)
+                call("sed_mhsa_fwd", q, k, v, o16, lse, Bx, H, N, Npad, 1 | (4 if p8 else 0))
                 x_mid = E(Bx, N, D) if sv else x_in
                 linear(p, "attn.proj", f_proj, o16, EPI_F32_RESID, D, res=x_in, outF=x_mid)
                 if dual:
                     call("sed_layernorm_fwd_dual", x_mid, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-6, 1.0, h2, h2s, mean2, rstd2, M, D)
                 else:
                     call("sed_layernorm_fwd", x_mid, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-6, 1.0, h2, None,
-                         mean2, rstd2, M, D, f16)
+                         mean2, rstd2, M, D, 1)
                 if f28:     # fc1's gb form whose epilogue also writes the e4m3 image of the activation beside it, for fc2's lo product
                     call("sed_gemm_nt_gb_e4m3", h2, W[p + "mlp.fc1.weight"].w, M, 4 * D, D, D, D, self.P(p + "mlp.fc1.bias"), act, 4 * pitch(f28),
                          self._wcorr_bias(W, p + "mlp.fc1.weight", h2, Bx, N), N)
@@ -523,12 +520,12 @@ class SedEngine:
                     x = x.clone()       # f_pool's backward reads the tensor it was given; the in-place blocks that follow must not touch it
         frame16 = None
         if want_frame:
-            frame16 = E(M, D, dt=A16)
+            frame16 = E(M, D, dt=ACT)
             fm, fr = (E(M), E(M)) if save else (None, None)
             # (DASM's head reads the tokens in fp32: the same pass writes them beside the 16-bit image)
             self._frame32 = E(M, D) if getattr(m, "dasm_head", None) is not None else None
             call("sed_layernorm_fwd", x, self.P("backbone.norm.weight"), self.P("backbone.norm.bias"), 1e-6, 1.0,
-                 frame16, self._frame32, fm, fr, M, D, f16)
+                 frame16, self._frame32, fm, fr, M, D, 1)
             if save:
                 ctx.update(x_final=x, fmean=fm, frstd=fr, frame16=frame16)
         return pooled, frame16, ctx
@@ -564,11 +561,9 @@ class SedEngine:
         N, S = 1 + F, Bx * tp
         M = S * N
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        A16 = self.act
-        f16 = 1 if A16 == F16 else 0
         SP = self._fpool_split_on(save)
-        mode = 4 if SP else f16
-        img = lambda k=D: E(M, 3 * k, dt=F16) if SP else E(M, k, dt=A16)       # operand image of an [M, k] activation
+        mode = 4 if SP else 1
+        img = lambda k=D: E(M, 3 * k, dt=F16) if SP else E(M, k, dt=ACT)       # operand image of an [M, k] activation
         wk = (lambda n: W[n].ws) if SP else (lambda n: W[n].w)
         pre = "f_pool_module."
         cur = E(M, D)
@@ -587,7 +582,7 @@ class SedEngine:
                     qkv = E(M, 3 * D)
                     gemm_nt(h16, wk(p + "attn.qkv.weight"), EPI_F32, outF=qkv)
                 else:
-                    qkv = E(M, 3 * D, dt=A16)
+                    qkv = E(M, 3 * D, dt=ACT)
                     gemm_nt(h16, wk(p + "attn.qkv.weight"), EPI_BF16, outH=qkv)
                 o16 = img()
                 call("sed_attn_short_fwd", qkv, o16, S, N, FPOOL_HEADS, o_kind(qkv), mode)
@@ -596,13 +591,13 @@ class SedEngine:
                 h2 = img()
                 mean2, rstd2 = stats()
                 call("sed_layernorm_fwd", x_mid, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-5, 1.0, h2, None, mean2, rstd2, M, D, mode)
-                hpre = E(M, 4 * D, dt=BF16 if save else A16)      # (GELU pre-activation: read by the backward only)
+                hpre = E(M, 4 * D, dt=BF16 if save else ACT)      # (GELU pre-activation: read by the backward only)
                 if SP:
                     act = E(M, 4 * D)
                     gemm_nt(h2, wk(p + "mlp.fc1.weight"), EPI_GELU32, bias=self.P(p + "mlp.fc1.bias"), outH=hpre, outF=act)
                     act = split3(act, M, 4 * D)         # forward operand and (first third) weight-gradient operand of fc2
                 else:
-                    act = E(M, 4 * D, dt=A16)
+                    act = E(M, 4 * D, dt=ACT)
                     gemm_nt(h2, wk(p + "mlp.fc1.weight"), EPI_GELU, bias=self.P(p + "mlp.fc1.bias"), outH=hpre, outH2=act)
                 x_out = E(M, D) if save else x_mid
                 gemm_nt(act, wk(p + "mlp.fc2.weight"), EPI_F32_RESID, bias=self.P(p + "mlp.fc2.bias"), res=x_mid, outF=x_out)
@@ -623,7 +618,25 @@ class SedEngine:
     def _relattn_terms2(self, M):
         """in_proj on two split-precision terms and linear_pos on plain operands (see `dec_terms2`; the 256^2 kernel's domain).  Decides the
         image the LayerNorm in front of `_relattn_fwd` writes, the table `_pos` hands out and the qkv entry point."""
-        return self.split and self.dec_terms2 and M >= 1024
+        return self.dec_terms2 and M >= 1024
+
+    def _ctx_ln_fwd(self, x, norm, scale, mean, rstd, plain=False, want32=False):
+        """LayerNorm `norm` (parameter prefix) of the context network's stream x [..., width] fp32 -> (operand image of the result for
+        the GEMM that follows, the fp32 result shaped like x or None).  Here the kernel writes the image itself: [hi | lo | hi] in split
+        precision, the plain f16 image when `plain` (`_relattn_terms2`)."""
+        Dm = x.shape[-1]
+        M = x.numel() // Dm
+        y16 = torch.empty(M, Dm if plain else 3 * Dm, dtype=ACT, device=x.device)
+        y32 = torch.empty(x.shape, dtype=F32, device=x.device) if want32 else None
+        call("sed_layernorm_fwd", x, self.P(norm + ".weight"), self.P(norm + ".bias"), 1e-5, scale, y16, y32, mean, rstd, M, Dm,
+             1 if plain else 4)
+        return y16, y32
+
+    _ctx_ln_bwd = "sed_layernorm_bwd"       # backward of `_ctx_ln_fwd`'s LayerNorm (entry point; same arguments in every form)
+
+    def _relattn_bias(self, pa, li):
+        """(in_proj bias, pos_bias_u, pos_bias_v) of the attention at prefix `pa` (layer `li`) as the qkv kernel reads them."""
+        return self.P(pa + "in_proj.bias"), self.P(pa + "pos_bias_u"), self.P(pa + "pos_bias_v")
 
     def _relattn_fwd(self, W, pa, li, ctx, pos16, hwt, yop, res, bias, save):
         """res + out_proj(relattn(y)): the rel-pos attention sub-block of every context network (Transformer-XL, Conformer, PMAM's 384-wide
@@ -636,29 +649,25 @@ class SedEngine:
         M, Dm, Da = B * T, res.shape[-1], H * 64
         dev = res.device
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        A16 = self.act
-        f16 = 1 if A16 == F16 else 0
-        SP = self.split
         T2 = self._relattn_terms2(M)
-        wk = (lambda n: W[pa + n].ws) if SP else (lambda n: W[pa + n].w)   # forward operand image of a weight
         # p = linear_pos(pos_emb), head-split [H, Rpad, 64] (+ transposed [H, 64, Rpad] for backward)
-        Ph = E(H, Rpad, 64, dt=A16)
-        Pt = torch.zeros(H, 64, Rpad, dtype=A16, device=dev) if save else None
-        ptmp = E(Rpad, Da, dt=A16)
+        Ph = E(H, Rpad, 64, dt=ACT)
+        Pt = torch.zeros(H, 64, Rpad, dtype=ACT, device=dev) if save else None
+        ptmp = E(Rpad, Da, dt=ACT)
         if T2:
             with ops.plain_precision():
                 gemm_nt(pos16, W[pa + "linear_pos.weight"].w, EPI_BF16, outH=ptmp)
         else:
-            gemm_nt(pos16, wk("linear_pos.weight"), EPI_BF16, outH=ptmp)
+            gemm_nt(pos16, W[pa + "linear_pos.weight"].ws, EPI_BF16, outH=ptmp)
         Ph.copy_(ptmp.view(Rpad, H, 64).permute(1, 0, 2))
         if save:
             Pt.copy_(ptmp.view(Rpad, H, 64).permute(1, 2, 0))
-        B16 = BF16 if save else A16   # backward-only tensors (row-major V, transposed q+u / q+v / K)
-        qu, k = [E(B * H, T, 64, dt=A16) for _ in range(2)]
+        B16 = BF16 if save else ACT   # backward-only tensors (row-major V, transposed q+u / q+v / K)
+        qu, k = [E(B * H, T, 64, dt=ACT) for _ in range(2)]
         v = E(B * H, T, 64, dt=B16)
-        qv = E(B * H, T, 64, dt=A16)
+        qv = E(B * H, T, 64, dt=ACT)
         use_pool = getattr(self, "_lease_ok", False) or not save
-        vt = self._zeros(("dec_vt", li, B, Tpad), (B * H, 64, Tpad), A16, dev, use_pool)
+        vt = self._zeros(("dec_vt", li, B, Tpad), (B * H, 64, Tpad), ACT, dev, use_pool)
         qut = kt = qvt = None
         if save:
             qut, kt, qvt = [self._zeros(("dec", li, j, B, Tpad), (B * H, 64, Tpad), B16, dev, use_pool) for j in range(3)]
@@ -666,73 +675,56 @@ class SedEngine:
             call("sed_gemm_qkv_w2s", yop, W[pa + "in_proj.weight"].ws, bias[0], M, Dm, H, T, Tpad,
                  qu, k, v, qut, kt, vt, qv, qvt, bias[1], bias[2], 3 if save else 1)
         else:
-            call("sed_gemm_qkv", yop, wk("in_proj.weight"), bias[0], M, 3 * Dm if SP else Dm, H, T, Tpad,
-                 qu, k, v, qut, kt, vt, qv, qvt, bias[1], bias[2], 3 if (save and f16) else f16)
-        o16 = E(M, Da, dt=F32 if SP else A16)
+            call("sed_gemm_qkv", yop, W[pa + "in_proj.weight"].ws, bias[0], M, 3 * Dm, H, T, Tpad,
+                 qu, k, v, qut, kt, vt, qv, qvt, bias[1], bias[2], 3 if save else 1)
+        o16 = E(M, Da)
         lse = E(B * H, T)
-        o16s = E(M, 3 * Da, dt=F16) if SP else None      # split-precision image of the attention output, written by the kernel itself
+        o16s = E(M, 3 * Da, dt=F16)      # split-precision image of the attention output, written by the kernel itself
         if hwt is None:
-            call("sed_relpos_attn_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0)
+            call("sed_relpos_attn_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, 1, 1)
         else:       # local window (decoder_win_len): the band kernels skip the key tiles no query of a workgroup sees
-            call("sed_relpos_attn_band_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, f16, 1 if SP else 0, hwt)
+            call("sed_relpos_attn_band_fwd", qu, qv, k, vt, Ph, o16, o16s, lse, B, H, T, Tpad, Rpad, 1, 1, hwt)
         out = E(*res.shape)
-        gemm_nt(o16s if SP else o16, wk("out_proj.weight"), EPI_F32_RESID, bias=self.P(pa + "out_proj.bias"), res=res, outF=out)
-        # (split precision: y16 / o16s are [M, 3 K] images whose first third is the f16 operand of the weight gradients)
+        gemm_nt(o16s, W[pa + "out_proj.weight"].ws, EPI_F32_RESID, bias=self.P(pa + "out_proj.bias"), res=res, outF=out)
+        # (y16 / o16s are [M, 3 K] images whose first third is the f16 operand of the weight gradients)
         return out, (dict(y16=yop, Ph=Ph, Pt=Pt, qu=qu, qut=qut, qv=qv, qvt=qvt, k=k, kt=kt, v=v, o16=o16, o16s=o16s, lse=lse) if save else None)
 
     @in_split_precision
     def _decoder_fwd(self, W, x, save):
-        """TransformerXLDecoder (src/models/transformer_decoder.py:110-122, transformerXL.py:31-35). x [B,T,D] f32."""
+        """TransformerXLDecoder (src/models/transformer_decoder.py:110-122, transformerXL.py:31-35) at the width of x [B, T, width] f32: the
+        one Transformer-XL schedule of every engine.  A variant overrides `_ctx_ln_fwd` / `_ctx_ln_bwd`, `_relattn_bias` and
+        `_relattn_sink`, never the schedule."""
         m = self.m
         dev = x.device
-        B, T, _ = x.shape
+        B, T, Dm = x.shape
         M = B * T
         T2 = self._relattn_terms2(M)
-        pos16, _, Rpad = self._pos(T, dev, want_plain=T2)
+        pos16, _, Rpad = self._pos(T, dev, Dm, want_plain=T2)
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        A16 = self.act
-        f16 = 1 if A16 == F16 else 0
         ctx = dict(B=B, T=T, Tpad=pad64(T), Rpad=Rpad, layers=[])
         cur = x
-        SP = self.split
         hwt = band_half_width(m, dev, T)
         for li in range(m.decoder_layer_num):
             p = f"decoder.encoder_blocks.{li}."
             pa = p + "attn."
-            in_scale = math.sqrt(D) if li == 0 else 1.0
-            wk = (lambda n: W[n].ws) if SP else (lambda n: W[n].w)   # forward operand image of a decoder weight
-            # split precision: the LayerNorm writes the [hi | lo | hi] image itself (two-term in_proj: the plain f16 image is all it reads)
-            y16 = E(M, 3 * D, dt=F16) if (SP and not T2) else E(M, D, dt=A16)
-            y32 = E(B, T, D)
+            in_scale = math.sqrt(Dm) if li == 0 else 1.0
             mean1, rstd1 = (E(M), E(M)) if save else (None, None)
-            call("sed_layernorm_fwd", cur, self.P(p + "norm1.weight"), self.P(p + "norm1.bias"), 1e-5, in_scale, y16,
-                 y32, mean1, rstd1, M, D, 4 if (SP and not T2) else f16)
-            x1, att = self._relattn_fwd(W, pa, li, ctx, pos16, hwt, y16, y32,
-                                        (self.P(pa + "in_proj.bias"), self.P(pa + "pos_bias_u"), self.P(pa + "pos_bias_v")), save)
-            h2 = E(M, D, dt=F32 if SP else A16)
-            h2s = E(M, 3 * D, dt=F16) if SP else None
+            # (two-term in_proj: the plain f16 image is all it reads)
+            y16, y32 = self._ctx_ln_fwd(cur, p + "norm1", in_scale, mean1, rstd1, plain=T2, want32=True)
+            x1, att = self._relattn_fwd(W, pa, li, ctx, pos16, hwt, y16, y32, self._relattn_bias(pa, li), save)
             mean2, rstd2 = (E(M), E(M)) if save else (None, None)
-            # (split precision: the [hi | lo | hi] image is the only form of LN2's output anybody reads -- the fc1 GEMM now, the weight
-            #  gradient of fc1 later through its first third)
-            call("sed_layernorm_fwd", x1, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-5, 1.0,
-                 h2s if SP else h2, None, mean2, rstd2, M, D, 4 if SP else f16)
-            if SP:
-                h2 = h2s
-            hpre = E(M, D, dt=BF16 if save else A16)      # (read by the backward only)
-            if SP:
-                act = E(M, D)
-                gemm_nt(h2s, wk(p + "mlp.fc1.weight"), EPI_GELU32, bias=self.P(p + "mlp.fc1.bias"), outH=hpre,
-                        outF=act)
-            else:
-                act = E(M, D, dt=A16)
-                gemm_nt(h2, wk(p + "mlp.fc1.weight"), EPI_GELU, bias=self.P(p + "mlp.fc1.bias"), outH=hpre, outH2=act)
-            x2 = E(B, T, D)
-            if SP:
-                act = split3(act, M, D)     # the fp32 activation is not read again: forward operand and (first third) dW operand of fc2
-            gemm_nt(act, wk(p + "mlp.fc2.weight"), EPI_F32_RESID,
-                    bias=self.P(p + "mlp.fc2.bias"), res=x1, outF=x2)
+            # (the [hi | lo | hi] image is the only form of LN2's output anybody reads -- the fc1 GEMM now, the weight gradient of fc1
+            #  later through its first third)
+            h2, _ = self._ctx_ln_fwd(x1, p + "norm2", 1.0, mean2, rstd2)
+            hpre = E(M, Dm, dt=BF16 if save else ACT)      # (read by the backward only)
+            act = E(M, Dm)
+            gemm_nt(h2, W[p + "mlp.fc1.weight"].ws, EPI_GELU32, bias=self.P(p + "mlp.fc1.bias"), outH=hpre, outF=act)
+            x2 = E(B, T, Dm)
+            act = split3(act, M, Dm)     # the fp32 activation is not read again: forward operand and (first third) dW operand of fc2
+            gemm_nt(act, W[p + "mlp.fc2.weight"].ws, EPI_F32_RESID, bias=self.P(p + "mlp.fc2.bias"), res=x1, outF=x2)
             if save:
-                # split precision: h2 / act are [M, 3 D] images whose first third is the f16 operand of the weight gradients
+                # y16 / h2 / act / o16s are the [M, 3 K] split-precision images the forward GEMMs consumed; their first third is the f16
+                # operand of the weight gradients (TN kernel, `_dw_accum`) -- no fp32 copies saved, no transposes in the backward
                 ctx["layers"].append(dict(att, x_in=cur, in_scale=in_scale, mean1=mean1, rstd1=rstd1, x1=x1, h2=h2, mean2=mean2,
                                           rstd2=rstd2, hpre=hpre, act=act))
             cur = x2
@@ -744,19 +736,16 @@ class SedEngine:
         new stream [M, D] fp32 and what `_swish_ffn_bwd` reads."""
         dev = xin.device
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        SP = self.split
-        f16 = 1 if self.act == F16 else 0
-        img = lambda: E(M, 3 * D, dt=F16) if SP else E(M, D, dt=self.act)
-        wk = (lambda n: W[n].ws) if SP else (lambda n: W[n].w)
+        img = lambda: E(M, 3 * D, dt=F16)       # [hi | lo | hi] operand image of an [M, D] activation
         y = img()
         mean, rstd = (E(M), E(M)) if save else (None, None)
-        call("sed_layernorm_fwd", xin, self.P(norm + ".weight"), self.P(norm + ".bias"), 1e-5, 1.0, y, None, mean, rstd, M, D, 4 if SP else f16)
+        call("sed_layernorm_fwd", xin, self.P(norm + ".weight"), self.P(norm + ".bias"), 1e-5, 1.0, y, None, mean, rstd, M, D, 4)
         h = E(M, D)
-        gemm_nt(y, wk(ff + ".0.weight"), EPI_F32, bias=self.P(ff + ".0.bias"), outF=h)
+        gemm_nt(y, W[ff + ".0.weight"].ws, EPI_F32, bias=self.P(ff + ".0.bias"), outF=h)
         a = img()
-        call("sed_swish_fwd", h, a, None, M, D, 4 if SP else f16)
+        call("sed_swish_fwd", h, a, None, M, D, 4)
         out = E(M, D)
-        gemm_nt(a, wk(ff + ".3.weight"), EPI_F32, bias=self.P(ff + ".3.bias"), outF=out)
+        gemm_nt(a, W[ff + ".3.weight"].ws, EPI_F32, bias=self.P(ff + ".3.bias"), outF=out)
         call("sed_scale_add_f32", out, xin, out, None, M * D, 0.5)
         return out, (dict(x_in=xin, y=y, mean=mean, rstd=rstd, h=h, a=a) if save else None)
 
@@ -771,15 +760,10 @@ class SedEngine:
         dev = x.device
         B, T, _ = x.shape
         M = B * T
-        SP = self.split
         T2 = self._relattn_terms2(M)
         pos16, _, Rpad = self._pos(T, dev, want_plain=T2)
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        A16 = self.act
-        f16 = 1 if A16 == F16 else 0
-        mode = 4 if SP else f16
-        img = lambda: E(M, 3 * D, dt=F16) if SP else E(M, D, dt=A16)
-        wk = (lambda n: W[n].ws) if SP else (lambda n: W[n].w)
+        img = lambda: E(M, 3 * D, dt=F16)       # [hi | lo | hi] operand image of an [M, D] activation
         ctx = dict(B=B, T=T, Tpad=pad64(T), Rpad=Rpad, layers=[])
         hwt = band_half_width(m, dev, T)
         cur = E(M, D)
@@ -789,31 +773,28 @@ class SedEngine:
             pa = p + "self_attn."
             x1, ffm = self._swish_ffn_fwd(W, p + "feed_forward_macaron", p + "norm_ff_macaron", cur, M, save)
             # ---- attention: x2 = x1 + out_proj(relattn(norm_mha(x1)))
-            y16 = E(M, 3 * D, dt=F16) if (SP and not T2) else E(M, D, dt=A16)
             mean1, rstd1 = (E(M), E(M)) if save else (None, None)
-            call("sed_layernorm_fwd", x1, self.P(p + "norm_mha.weight"), self.P(p + "norm_mha.bias"), 1e-5, 1.0, y16, None, mean1, rstd1,
-                 M, D, 4 if (SP and not T2) else f16)
-            x2, att = self._relattn_fwd(W, pa, li, ctx, pos16, hwt, y16, x1,
-                                        (self.P(pa + "in_proj.bias"), self.P(pa + "pos_bias_u"), self.P(pa + "pos_bias_v")), save)
+            y16, _ = self._ctx_ln_fwd(x1, p + "norm_mha", 1.0, mean1, rstd1, plain=T2)
+            x2, att = self._relattn_fwd(W, pa, li, ctx, pos16, hwt, y16, x1, self._relattn_bias(pa, li), save)
             # ---- convolution module: x3 = x2 + pointwise_conv2(swish(norm(depthwise(glu(pointwise_conv1(norm_conv(x2)))))))
             pc = p + "conv_module."
             yc = img()
             meanc, rstdc = (E(M), E(M)) if save else (None, None)
             call("sed_layernorm_fwd", x2, self.P(p + "norm_conv.weight"), self.P(p + "norm_conv.bias"), 1e-5, 1.0, yc, None, meanc, rstdc,
-                 M, D, mode)
+                 M, D, 4)
             xp = E(M, 2 * D)
-            gemm_nt(yc, wk(pc + "pointwise_conv1.weight"), EPI_F32, bias=self.P(pc + "pointwise_conv1.bias"), outF=xp)
+            gemm_nt(yc, W[pc + "pointwise_conv1.weight"].ws, EPI_F32, bias=self.P(pc + "pointwise_conv1.bias"), outF=xp)
             ys = img()
             conv, cmean, crstd = (E(M, D), E(M), E(M)) if save else (None, None, None)
             call("sed_conv_glu_dw_fwd", xp, self.P(pc + "depthwise_conv.weight"), self.P(pc + "depthwise_conv.bias"),
-                 self.P(pc + "norm.weight"), self.P(pc + "norm.bias"), 1e-5, ys, None, conv, cmean, crstd, B, T, D, mode)
+                 self.P(pc + "norm.weight"), self.P(pc + "norm.bias"), 1e-5, ys, None, conv, cmean, crstd, B, T, D, 4)
             x3 = E(M, D)
-            gemm_nt(ys, wk(pc + "pointwise_conv2.weight"), EPI_F32_RESID, bias=self.P(pc + "pointwise_conv2.bias"), res=x2, outF=x3)
+            gemm_nt(ys, W[pc + "pointwise_conv2.weight"].ws, EPI_F32_RESID, bias=self.P(pc + "pointwise_conv2.bias"), res=x2, outF=x3)
             x4, ff = self._swish_ffn_fwd(W, p + "feed_forward", p + "norm_ff", x3, M, save)
             out = E(M, D)
             fmean, frstd = (E(M), E(M)) if save else (None, None)
             call("sed_layernorm_fwd", x4, self.P(p + "norm_final.weight"), self.P(p + "norm_final.bias"), 1e-5, 1.0, None, out, fmean, frstd,
-                 M, D, f16)
+                 M, D, 1)
             if save:
                 ctx["layers"].append(dict(att, ffm=ffm, ff=ff, x1=x1, mean1=mean1, rstd1=rstd1, x2=x2, yc=yc, meanc=meanc, rstdc=rstdc, xp=xp,
                                           ys=ys, conv=conv, cmean=cmean, crstd=crstd, x4=x4, fmean=fmean, frstd=frstd))
@@ -952,21 +933,13 @@ class SedEngine:
         n_out = W["mlm_mlp.2.weight"].w.shape[0]
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=xd.device)
         hpre = E(M, Dm, dt=hpre_dt)
-        if self.split:
-            act = E(M, Dm)
-            pred = E(B, Tdec, n_out)
-            with ops.split_precision():
-                xd16 = split3(xd.view(M, Dm), M, Dm)
-                gemm_nt(xd16, W["mlm_mlp.0.weight"].ws, EPI_GELU32, bias=self.P("mlm_mlp.0.bias"), outH=hpre, outF=act)
-                act = split3(act, M, Dm)      # split images: the first third is the weight-gradient operand
-                gemm_nt(act, W["mlm_mlp.2.weight"].ws, EPI_F32, bias=self.P("mlm_mlp.2.bias"), outF=pred.view(M, n_out))
-        else:
-            pred = E(B, Tdec, n_out)
-            xd16 = E(M, Dm, dt=self.act)
-            call("sed_cast_f32_bf16", xd, xd16, M * Dm, is_f16(xd16))
-            act = E(M, Dm, dt=self.act)
-            gemm_nt(xd16, W["mlm_mlp.0.weight"].w, EPI_GELU, bias=self.P("mlm_mlp.0.bias"), outH=hpre, outH2=act)
-            gemm_nt(act, W["mlm_mlp.2.weight"].w, EPI_F32, bias=self.P("mlm_mlp.2.bias"), outF=pred.view(M, n_out))
+        act = E(M, Dm)
+        pred = E(B, Tdec, n_out)
+        with ops.split_precision():
+            xd16 = split3(xd.view(M, Dm), M, Dm)
+            gemm_nt(xd16, W["mlm_mlp.0.weight"].ws, EPI_GELU32, bias=self.P("mlm_mlp.0.bias"), outH=hpre, outF=act)
+            act = split3(act, M, Dm)      # split images: the first third is the weight-gradient operand
+            gemm_nt(act, W["mlm_mlp.2.weight"].ws, EPI_F32, bias=self.P("mlm_mlp.2.bias"), outF=pred.view(M, n_out))
         return pred, dict(xd16=xd16, hpre=hpre, act=act)
 
     def _mlm_head_bwd(self, W, ctx, dpred, G):
@@ -984,7 +957,7 @@ class SedEngine:
         m = self.m
         B, Tdec, Dm = xd.shape
         if m.mlm:
-            out["mlm_pred"], hctx = self._mlm_head_fwd(W, xd, self.act)
+            out["mlm_pred"], hctx = self._mlm_head_fwd(W, xd, ACT)
         elif self._wide_head(save):
             # any class count (AudioSet-Strong's 407): logits on the fp32 matrix instruction + the transposing sigmoid / pooling kernel
             # (dasm.wide_head_fwd); the dedicated kernels serve the 10-class DESED head
@@ -1019,7 +992,7 @@ class SedEngine:
         bin_ = self.P(pre + "frequency_att.in_proj_bias")
         q = E(1, D)
         call("sed_small_linear", self.P(pre + "f_att_token").reshape(1, D), win[:D], bin_[:D], q, 1, D, D, 0)
-        kv16 = E(B * N, 2 * D, dt=self.act)
+        kv16 = E(B * N, 2 * D, dt=ACT)
         gemm_nt(frame16, W[pre + "frequency_att.in_proj_weight"].w[D:], EPI_BF16, bias=bin_[D:], outH=kv16)
         pooled = E(B, D)
         probs = E(B * H, N - 2) if save else None
@@ -1321,6 +1294,21 @@ class SedEngine:
         t, self._genc16 = getattr(self, "_genc16", None), None
         return t[1] if (t is not None and t[0] is g and t[2] == g._version) else None
 
+    def _on_dw_stream(self, run, *operands):
+        """`run()` (weight-gradient work reading `operands`) on the weight-gradient side stream -- see `dw_side`; on the current stream
+        while the kernel timer instruments a step or off the GPU.  `_join_dw` orders the current stream behind it."""
+        if not (self.dw_side and ops.TIMER is None and operands[0].is_cuda):
+            return run()
+        dev = operands[0].device
+        if self._dw_stream is None:
+            self._dw_stream = torch.cuda.Stream(device=dev)
+        self._dw_stream.wait_stream(torch.cuda.current_stream(dev))        # dY, the saved operand and the zeroed arena are ready
+        with torch.cuda.stream(self._dw_stream):
+            run()
+        for t in operands:      # the caching allocator must not hand these out again before the side stream has read them
+            t.record_stream(self._dw_stream)
+        self._dw_pending = True
+
     def _dw_accum(self, dy, x, M, gW, bias=None, dy16=None, k_in=None):
         """gW += dy^T x (weight gradient), bias += column sums of dy.  dy [M, n_out] f32 or bf16, x [M, k_in] (saved forward
         operand, 16-bit or f32); gW / bias are arena views or None.  Returns dy as a bf16 [M, n_out] tensor (operand of the
@@ -1359,18 +1347,7 @@ class SedEngine:
                         transpose_bf16(dy16[Mt:], M - Mt, n_out, gT)
                         transpose_bf16(x[Mt:], M - Mt, k_in, xT, ld=ldx)
                         gemm_dw(gT, xT, gW)
-                if self.dw_side and ops.TIMER is None and dy16.is_cuda:
-                    if self._dw_stream is None:
-                        self._dw_stream = torch.cuda.Stream(device=dev)
-                    main = torch.cuda.current_stream(dev)
-                    self._dw_stream.wait_stream(main)        # dY, the saved operand and the zeroed arena are ready
-                    with torch.cuda.stream(self._dw_stream):
-                        run()
-                    dy16.record_stream(self._dw_stream)      # the caching allocator must not hand these out again before the
-                    x.record_stream(self._dw_stream)         # side stream has read them
-                    self._dw_pending = True
-                else:
-                    run()
+                self._on_dw_stream(run, dy16, x)
             return dy16
         Mpad = pad64(M)
         g16 = E(M, n_out, dt=BF16) if dy.dtype == F32 else None
@@ -1454,27 +1431,26 @@ class SedEngine:
         ectx["layers"][li] = None  # free saved activations
         return g
 
-    def _relattn_sink(self, Gl, pa, dev):
-        """Where `_relattn_bwd` adds the parameter gradients of the attention at prefix `pa`, as arena views: (weight, bias) of out_proj
-        and in_proj, linear_pos's weight, pos_bias_u / v.  `Gl` names nothing in a frozen context network; the kernel still writes
-        du / dv somewhere."""
+    def _relattn_sink(self, Gl, pa, li, dctx, dev):
+        """Where `_relattn_bwd` adds the parameter gradients of the attention at prefix `pa` (layer `li` of the forward behind `dctx`),
+        as arena views: (weight, bias) of out_proj and in_proj, linear_pos's weight, pos_bias_u / v.  `Gl` names nothing in a frozen
+        context network; the kernel still writes du / dv somewhere."""
         scratch_uv = torch.zeros(2, D, dtype=F32, device=dev)
         du, dv = Gl(pa + "pos_bias_u"), Gl(pa + "pos_bias_v")
         return dict(out_proj=(Gl(pa + "out_proj.weight"), Gl(pa + "out_proj.bias")), linear_pos=Gl(pa + "linear_pos.weight"),
                     in_proj=(Gl(pa + "in_proj.weight"), Gl(pa + "in_proj.bias")),
                     pos_bias_u=du if du is not None else scratch_uv[0], pos_bias_v=dv if dv is not None else scratch_uv[1])
 
-    def _relattn_bwd(self, W, pa, L, dctx, posT16, hwt, g2, sink, out_k_in, residual):
+    def _relattn_bwd(self, W, pa, L, dctx, posT16, hwt, g2, sink, residual):
         """Backward of `_relattn_fwd` given the stream gradient g2 [M, model width] fp32 and the forward's saved tensors `L`.  `sink`: the
-        gradient destinations by role (see `_relattn_sink`; linear_pos None = frozen: only the input gradient is computed); `out_k_in`:
-        `k_in` of out_proj's `_dw_accum`.  The gradient at the normalised input is added into `residual` (fp32 [M, model width]) when
-        given, else returned in a new tensor."""
+        gradient destinations by role (see `_relattn_sink`; linear_pos None = frozen: only the input gradient is computed).  The
+        gradient at the normalised input is added into `residual` (fp32 [M, model width]) when given, else returned in a new tensor."""
         B, T, Tpad, Rpad = dctx["B"], dctx["T"], dctx["Tpad"], dctx["Rpad"]
         M, Dm, Da = B * T, g2.shape[1], H * 64
         dev = g2.device
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         train = sink["linear_pos"] is not None
-        g16 = self._dw_accum(g2, L["o16s"] if L.get("o16s") is not None else L["o16"], M, *sink["out_proj"], k_in=out_k_in)
+        g16 = self._dw_accum(g2, L["o16s"], M, *sink["out_proj"], k_in=Da)
         do16 = E(M, Da, dt=BF16)
         gemm_nt(g16, W[pa + "out_proj.weight"].wt, EPI_BF16, outH=do16)
         dqkv = E(M, 3 * Da, dt=BF16)
@@ -1505,11 +1481,14 @@ class SedEngine:
         return dy
 
     def _decoder_bwd(self, W, dctx, g, G, trainable):
+        """Backward of `_decoder_fwd` given g = d(output) [B, T, width]; -> d(input).  Parameter gradients go to the views `G` names
+        (the attention's: where `_relattn_sink` says); none is computed when `trainable` is false.  (The PMAM form of the sink needs
+        `dctx["slots"]`: the views of `_grad_slots` made with `dec_train` = `trainable`, as `PmamEngine._context_bwd` leaves them.)"""
         m = self.m
-        B, T = dctx["B"], dctx["T"]
+        B, T, Dm = g.shape
         M = B * T
         dev = g.device
-        _, posT16, _ = self._pos(T, dev)
+        _, posT16, _ = self._pos(T, dev, Dm)
         hwt = band_half_width(m, dev, T)
         Gl = G if trainable else (lambda n: None)
         g = g.contiguous()
@@ -1517,17 +1496,17 @@ class SedEngine:
             p = f"decoder.encoder_blocks.{li}."
             pa = p + "attn."
             L = dctx["layers"][li]
-            g2 = g.view(M, D)
+            g2 = g.view(M, Dm)
             # MLP branch
             dln = self._mlp_bwd(W, p + "mlp.fc1", p + "mlp.fc2", g2, L["h2"], L["hpre"], L["act"], M, Gl, residual=None)
-            call("sed_layernorm_bwd", dln, L["x1"], L["mean2"], L["rstd2"], self.P(p + "norm2.weight"), 1.0, g2, 1,
-                 Gl(p + "norm2.weight"), Gl(p + "norm2.bias"), M, D)
+            call(self._ctx_ln_bwd, dln, L["x1"], L["mean2"], L["rstd2"], self.P(p + "norm2.weight"), 1.0, g2, 1,
+                 Gl(p + "norm2.weight"), Gl(p + "norm2.bias"), M, Dm)
             del dln
             # attention branch: x1 = y + out_proj(relattn(y)),  y = LN1(in_scale * x_in)
-            self._relattn_bwd(W, pa, L, dctx, posT16, hwt, g2, self._relattn_sink(Gl, pa, dev), D, residual=g2)
-            gnew = torch.empty(B, T, D, dtype=F32, device=dev)
-            call("sed_layernorm_bwd", g2, L["x_in"], L["mean1"], L["rstd1"], self.P(p + "norm1.weight"), L["in_scale"],
-                 gnew.view(M, D), 0, Gl(p + "norm1.weight"), Gl(p + "norm1.bias"), M, D)
+            self._relattn_bwd(W, pa, L, dctx, posT16, hwt, g2, self._relattn_sink(Gl, pa, li, dctx, dev), residual=g2)
+            gnew = torch.empty(B, T, Dm, dtype=F32, device=dev)
+            call(self._ctx_ln_bwd, g2, L["x_in"], L["mean1"], L["rstd1"], self.P(p + "norm1.weight"), L["in_scale"],
+                 gnew.view(M, Dm), 0, Gl(p + "norm1.weight"), Gl(p + "norm1.bias"), M, Dm)
             g = gnew
             dctx["layers"][li] = None
         return g
@@ -1590,8 +1569,8 @@ class SedEngine:
                  Gl(p + "norm_conv.weight"), Gl(p + "norm_conv.bias"), M, D)
             del dys, dxp
             # ---- attention
-            dln = self._relattn_bwd(W, pa, L, dctx, posT16, hwt, g2, self._relattn_sink(Gl, pa, dev), D, residual=None)
-            call("sed_layernorm_bwd", dln, L["x1"], L["mean1"], L["rstd1"], self.P(p + "norm_mha.weight"), 1.0, g2, 1,
+            dln = self._relattn_bwd(W, pa, L, dctx, posT16, hwt, g2, self._relattn_sink(Gl, pa, li, dctx, dev), residual=None)
+            call(self._ctx_ln_bwd, dln, L["x1"], L["mean1"], L["rstd1"], self.P(p + "norm_mha.weight"), 1.0, g2, 1,
                  Gl(p + "norm_mha.weight"), Gl(p + "norm_mha.bias"), M, D)
             del dln
             self._swish_ffn_bwd(W, p + "feed_forward_macaron", p + "norm_ff_macaron", L["ffm"], g2, M, Gl)

@@ -20,9 +20,9 @@ import torch
 
 from . import ops
 
-from .engine import SedEngine, _W, D, H, version_key, band_half_width, in_split_precision
+from .engine import SedEngine, _W, ACT, D, H, version_key
 from .ops import BF16, F16, F32, call, h2d, gemm_nt, gemm_nt_cols, gemm_dw, gemm_dw_tn, dw_tn_ok, pad64, transpose_bf16, split3, is_f16
-from .ops import EPI_F32, EPI_F32_RESID, EPI_BF16, EPI_GELU32
+from .ops import EPI_F32, EPI_F32_RESID, EPI_BF16
 
 HD_PAD = 64          # head width the attention kernels are built for
 SQRT2 = math.sqrt(2.0)
@@ -49,9 +49,7 @@ class PmamEngine(SedEngine):
         self.lora_skinny = True
         self.small_dw = True
         self.cg_fused16 = True
-        if not self.split:
-            raise RuntimeError("the PMAM path runs its 384-wide context network in split precision (engine.split, f16 forward)")
-        self.dec_terms2 = False      # (its own context-network schedule below keeps three terms in every GEMM)
+        self.dec_terms2 = False      # (this context network keeps three split-precision terms in every GEMM)
         self._drop_gen = None
 
     def _dropout_generator(self):
@@ -187,15 +185,14 @@ class PmamEngine(SedEngine):
         dev = self.P("out_norm.weight").device
         mats, vecs, geo = self._image_specs(dev)
         merged = m.lora_merged or not m.lora_r
-        kind_act = 2 if self.act == F16 else 0
         sbits = int(torch.tensor(float(m.lora_scaling), dtype=torch.float32).view(torch.int32)) if m.lora_r else 0
         statics = self.__dict__.setdefault("_static_keys", {})
 
         def entry(name, R, C, split, kind):
             ent = self.cache.get(name)
             if ent is None or ent.w.device != dev or ent.w.shape != (R, C):
-                wdt = BF16 if kind == "bf16" else self.act
-                ent = _W(torch.empty(R, C, dtype=wdt, device=dev), torch.empty(C, R, dtype=BF16, device=dev) if kind == "act" else None)
+                ent = _W(torch.empty(R, C, dtype=BF16 if kind == "bf16" else ACT, device=dev),
+                         torch.empty(C, R, dtype=BF16, device=dev) if kind == "act" else None)
                 self.cache[name] = ent
             if split and (ent.ws is None or ent.ws.device != dev):
                 ent.ws = torch.empty(R, 3 * C, dtype=F16, device=dev)
@@ -206,7 +203,7 @@ class PmamEngine(SedEngine):
             ent = entry(name, R, C, split, kind)
             use_lora = lora is not None and not merged
             return [self.P(master).data_ptr(), ent.wt.data_ptr() if (kind == "act" and need_t) else 0, ent.w.data_ptr(),
-                    ent.ws.data_ptr() if split else 0, R, C, kind_act if kind == "act" else 0, tiles,
+                    ent.ws.data_ptr() if split else 0, R, C, 2 if kind == "act" else 0, tiles,
                     plan[0].data_ptr() if plan is not None else 0, plan[1].data_ptr() if plan is not None else 0,
                     self.P(lora + ".lora_A").data_ptr() if use_lora else 0, self.P(lora + ".lora_B").data_ptr() if use_lora else 0,
                     m.lora_r if use_lora else 0, sbits if use_lora else 0, 0, 0]
@@ -224,7 +221,7 @@ class PmamEngine(SedEngine):
             if any(p.requires_grad for p in parts):
                 live.append(spec)
                 continue
-            key = version_key(parts, (merged, bool(need_t), self.act))
+            key = version_key(parts, (merged, bool(need_t)))
             if statics.get(name) != key or name not in self.cache:
                 stale.append(spec)
                 statics[name] = key
@@ -232,7 +229,7 @@ class PmamEngine(SedEngine):
             if not specs:
                 continue
             ptrs = tuple(self.P(sp[1]).data_ptr() for sp in specs) + tuple(self.P(sp[5] + ".lora_A").data_ptr() for sp in specs if sp[5]) + \
-                (bool(need_t), merged, self.act, len(specs))
+                (bool(need_t), merged, len(specs))
             if cached and getattr(self, "_wimg_key", None) == ptrs:
                 desc, n, tiles = self._wimg_desc
             else:
@@ -276,21 +273,20 @@ class PmamEngine(SedEngine):
         dev = x.device
         N = 2 + 12 * tp
         M = Bx * N
-        f16 = is_f16(W["backbone.patch_embed.proj.weight"].w)
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         pre = "f_pool_module."
-        h16 = E(M, D, dt=self.act)
+        h16 = E(M, D, dt=ACT)
         pm, pr = (E(M), E(M)) if save else (None, None)
-        call("sed_layernorm_fwd", x, self.P("out_norm.weight"), self.P("out_norm.bias"), 1e-5, 1.0, h16, None, pm, pr, M, D, f16)
+        call("sed_layernorm_fwd", x, self.P("out_norm.weight"), self.P("out_norm.bias"), 1e-5, 1.0, h16, None, pm, pr, M, D, 1)
         win = self.P(pre + "frequency_att.in_proj_weight")
         bin_ = self.P(pre + "frequency_att.in_proj_bias")
         q = E(1, D)
         call("sed_small_linear", self.P(pre + "f_att_token").reshape(1, D), win[:D], bin_[:D], q, 1, D, D, 0)
-        kv16 = E(M, 2 * D, dt=self.act)
+        kv16 = E(M, 2 * D, dt=ACT)
         gemm_nt(h16, W[pre + "frequency_att.in_proj_weight"].w[D:], EPI_BF16, bias=bin_[D:], outH=kv16)
-        att16 = E(Bx * tp, D, dt=self.act)
+        att16 = E(Bx * tp, D, dt=ACT)
         probs = E(Bx * tp, 6, 12) if save else None
-        call("sed_fpool_attn_fwd", kv16, q, att16, None, probs, Bx, N, tp, f16)
+        call("sed_fpool_attn_fwd", kv16, q, att16, None, probs, Bx, N, tp, 1)
         pooled = E(Bx, tp, D)
         gemm_nt(att16, W[pre + "frequency_att.out_proj.weight"].w, EPI_F32, bias=self.P(pre + "frequency_att.out_proj.bias"),
                 outF=pooled.view(Bx * tp, D))
@@ -305,7 +301,6 @@ class PmamEngine(SedEngine):
         m = self.m
         dev = mel.device
         B, _, T = mel.shape
-        f16 = 1 if self.act == F16 else 0
         E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
         Hc, Wc = T, 128
         X = None
@@ -346,9 +341,9 @@ class PmamEngine(SedEngine):
                 call("sed_conv0_fwd16", mel, self.P("cnn.cnn.conv0.weight").detach(), self.P("cnn.cnn.conv0.bias").detach(), Y, B, T,
                      sums[i, 0] if train else None, sums[i, 1] if train else None)
             else:
-                col = E(Mi, Kp, dt=self.act)
+                col = E(Mi, Kp, dt=ACT)
                 if i == 0:
-                    call("sed_conv0_im2col", mel, col, B, T, f16)
+                    call("sed_conv0_im2col", mel, col, B, T, 1)
                 else:
                     call("sed_conv3x3_im2col", X, col, B, Hc, Wc, cin, max(64, cin), Kp)
                 if aux["dyn"]:
@@ -371,8 +366,8 @@ class PmamEngine(SedEngine):
             fused16 = self.cg_fused16 and self.small_dw and self.dw_tn and co == 16 and ldy == 16 and Mi >= 1024
             Z = L = None
             if not fused16:
-                Z = E(Mi, Cp, dt=self.act)
-                call("sed_bn_act", Y, ldy, a, b, Z, Mi, co, Cp, f16)
+                Z = E(Mi, Cp, dt=ACT)
+                call("sed_bn_act", Y, ldy, a, b, Z, Mi, co, Cp, 1)
                 L = E(Mi, ldy)
                 if ldy < Np:
                     gemm_nt_cols(Z, W[f"cnn.cnn.cg{i}.linear.weight"].w, EPI_F32, co, bias=aux["gbias"], outF=L)
@@ -381,7 +376,7 @@ class PmamEngine(SedEngine):
             ph, pw = m.cnn_pooling[i]
             last = i + 1 == len(self.cnn_aux)
             Cpo = max(64, co)
-            Xn = None if last else E(B, Hc // ph, Wc // pw, Cpo, dt=self.act)
+            Xn = None if last else E(B, Hc // ph, Wc // pw, Cpo, dt=ACT)
             if last:
                 feat = E(B * (Hc // ph) * (Wc // pw), co)
             mask = None
@@ -393,11 +388,11 @@ class PmamEngine(SedEngine):
                 # 16 filters: z = Y a + b, l = W_g z + b_g (fp32, 256 FMAs per pixel), gate, dropout and pooling in one pass over Y; the
                 # backward's operands -- the logits and the 16-column 16-bit image of z -- are side outputs of a saving pass
                 if save:
-                    L, Z = E(Mi, 16), E(Mi, 16, dt=self.act)
+                    L, Z = E(Mi, 16), E(Mi, 16, dt=ACT)
                 call("sed_cg_gate16_pool", Y, ldy, a, b, self.P(f"cnn.cnn.cg{i}.linear.weight").detach(), self.P(f"cnn.cnn.cg{i}.linear.bias").detach(),
-                     mask, float(scale), L, Z, Xn, feat, B, Hc, Wc, Cpo, ph, pw, f16)
+                     mask, float(scale), L, Z, Xn, feat, B, Hc, Wc, Cpo, ph, pw, 1)
             else:
-                call("sed_cg_pool", Y, ldy, a, b, L, ldy, mask, float(scale), Xn, feat, B, Hc, Wc, co, Cpo, ph, pw, f16)
+                call("sed_cg_pool", Y, ldy, a, b, L, ldy, mask, float(scale), Xn, feat, B, Hc, Wc, co, Cpo, ph, pw, 1)
             if save:
                 layers.append(dict(col=col, mel=mel if direct0 else None, Y=Y, a=a, b=b, ah=ah, bh=bh, Z=Z, L=L, mask=mask, scale=scale, H=Hc,
                                    W=Wc, ldy=ldy, dyn=dynctx if aux["dyn"] else None))
@@ -460,44 +455,33 @@ class PmamEngine(SedEngine):
         return dout
 
     # ------------------------------------------------------------------ 384-wide context network on the 64-wide attention kernels
-    @in_split_precision
-    def _decoder_fwd(self, W, x, save):
-        m = self.m
-        dev = x.device
-        B, T, Dd = x.shape
-        M = B * T
-        pos16, _, Rpad = self._pos(T, dev, Dd)
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        ctx = dict(B=B, T=T, Tpad=pad64(T), Rpad=Rpad, layers=[])
-        cur = x
-        hwt = band_half_width(m, dev, T)
-        for li in range(m.decoder_layer_num):
-            p = f"decoder.encoder_blocks.{li}."
-            aux = self.dec_aux[li]
-            in_scale = math.sqrt(Dd) if li == 0 else 1.0
-            y32 = E(B, T, Dd)
-            mean1, rstd1 = (E(M), E(M)) if save else (None, None)
-            call("sed_ln_fwd_any", cur, self.P(p + "norm1.weight"), self.P(p + "norm1.bias"), 1e-5, in_scale, None, y32, mean1, rstd1,
-                 M, Dd, 1)
-            # (the weights at this prefix are the padded-head images: the shared attention path runs H * HD_PAD wide)
-            x1, att = self._relattn_fwd(W, p + "attn.", li, ctx, pos16, hwt, split3(y32, M, Dd), y32, (aux["bin"], aux["u"], aux["v"]), save)
-            h2 = E(M, Dd)
-            mean2, rstd2 = (E(M), E(M)) if save else (None, None)
-            call("sed_ln_fwd_any", x1, self.P(p + "norm2.weight"), self.P(p + "norm2.bias"), 1e-5, 1.0, None, h2, mean2, rstd2, M, Dd, 1)
-            hpre = E(M, Dd, dt=BF16 if save else self.act)      # (read by the backward only)
-            act = E(M, Dd)
-            h2 = split3(h2, M, Dd)
-            gemm_nt(h2, W[p + "mlp.fc1.weight"].ws, EPI_GELU32, bias=self.P(p + "mlp.fc1.bias"), outH=hpre, outF=act)
-            x2 = E(B, T, Dd)
-            act = split3(act, M, act.shape[1])
-            gemm_nt(act, W[p + "mlp.fc2.weight"].ws, EPI_F32_RESID, bias=self.P(p + "mlp.fc2.bias"), res=x1, outF=x2)
-            if save:
-                # y16 / h2 / act / o16s are the [M, 3 K] split-precision images the forward GEMMs consumed; their first third is the f16
-                # operand of the weight gradients (TN kernel, engine.py `_dw_accum`) -- no fp32 copies saved, no transposes in the backward
-                ctx["layers"].append(dict(att, x_in=cur, in_scale=in_scale, mean1=mean1, rstd1=rstd1, x1=x1, h2=h2, mean2=mean2, rstd2=rstd2,
-                                          hpre=hpre, act=act))
-            cur = x2
-        return cur, ctx
+    # SedEngine's Transformer-XL schedule at decoder_dim; what differs here are these pieces.  (The weights at the attention's prefix are
+    # the padded-head images: the shared attention path runs H * HD_PAD wide.)
+    def _ctx_ln_fwd(self, x, norm, scale, mean, rstd, plain=False, want32=False):
+        """Any width: `sed_ln_fwd_any` to fp32, then the [hi | lo | hi] image of that (`dec_terms2` is off here: never `plain`)."""
+        Dm = x.shape[-1]
+        M = x.numel() // Dm
+        y32 = torch.empty(x.shape if want32 else (M, Dm), dtype=F32, device=x.device)
+        call("sed_ln_fwd_any", x, self.P(norm + ".weight"), self.P(norm + ".bias"), 1e-5, scale, None, y32, mean, rstd, M, Dm, 1)
+        return split3(y32, M, Dm), (y32 if want32 else None)
+
+    _ctx_ln_bwd = "sed_ln_bwd_any"
+
+    def _relattn_bias(self, pa, li):
+        aux = self.dec_aux[li]      # (the padded vectors `_weights` gathered)
+        return aux["bin"], aux["u"], aux["v"]
+
+    def _relattn_sink(self, Gl, pa, li, dctx, dev):
+        """The gradient images (padded heads) in the zeroed slots of `_grad_slots` that `_context_bwd` left in `dctx`; one scatter
+        launch after the walk un-pads them."""
+        Dd, Dp = self.m.decoder_dim, H * HD_PAD
+        slots = dctx["slots"]
+        if ("gwo", li) not in slots:       # frozen: `_grad_slots` made no images for the context network
+            Z = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
+            return dict(out_proj=(None, None), linear_pos=None, in_proj=(None, None), pos_bias_u=Z(Dp), pos_bias_v=Z(Dp))
+        return dict(out_proj=(slots[("gwo", li)].view(Dd, Dp), Gl(pa + "out_proj.bias")), linear_pos=slots[("gwp", li)].view(Dp, Dd),
+                    in_proj=(slots[("gwi", li)].view(3 * Dp, Dd), slots[("gbi", li)]),
+                    pos_bias_u=slots[("du", li)], pos_bias_v=slots[("dv", li)])
 
     # ------------------------------------------------------------------ stages of SedEngine.forward (passt_cnn.py:31-88)
     _mlm_c = True               # the merged sequence is decoder_dim wide
@@ -573,7 +557,7 @@ class PmamEngine(SedEngine):
                 hctx["query_grads"] = list(getattr(m, "_dasm_query_grads", ()) or ()) or None
             return hctx
         if m.mlm:
-            out["mlm_pred"], hctx = self._mlm_head_fwd(W, xd, BF16 if save else self.act)
+            out["mlm_pred"], hctx = self._mlm_head_fwd(W, xd, BF16 if save else ACT)
             return hctx
         return super()._heads_fwd(W, xd, ectx, opt, save, out)      # classifier + sigmoid + linear-softmax pooling (passt_cnn.py:74-86)
 
@@ -616,17 +600,7 @@ class PmamEngine(SedEngine):
             call("sed_lora_colreduce", g16, 0, M, n_out, g16.shape[1], u, sl.r, sl.s, sl.gB, 1)
             call("sed_lora_colreduce", x, is_f16(x), M, kin, ldx, du, sl.r, 1.0, sl.gA, 0)
 
-        if self.dw_side and ops.TIMER is None and g16.is_cuda:
-            if self._dw_stream is None:
-                self._dw_stream = torch.cuda.Stream(device=dev)
-            self._dw_stream.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(self._dw_stream):
-                run()
-            g16.record_stream(self._dw_stream)
-            x.record_stream(self._dw_stream)
-            self._dw_pending = True
-        else:
-            run()
+        self._on_dw_stream(run, g16, x)
         return g16
 
     def _dw_swapped_tn(self, M, n, k):
@@ -808,41 +782,6 @@ class PmamEngine(SedEngine):
                 call("sed_col2im3x3", dcol, Kp, dout, B, Hc, Wc, cin)
             cctx["layers"][i] = None
 
-    def _decoder_bwd(self, W, dctx, g, G, trainable, slots):
-        m = self.m
-        B, T = dctx["B"], dctx["T"]
-        Dd = m.decoder_dim
-        Dp = H * HD_PAD
-        M = B * T
-        dev = g.device
-        Z = lambda *s: torch.zeros(*s, dtype=F32, device=dev)
-        _, posT16, _ = self._pos(T, dev, Dd)
-        hwt = band_half_width(m, dev, T)
-        Gl = G if trainable else (lambda n: None)
-        g = g.contiguous()
-        for li in range(m.decoder_layer_num - 1, -1, -1):
-            p = f"decoder.encoder_blocks.{li}."
-            L = dctx["layers"][li]
-            g2 = g.view(M, Dd)
-            dln = self._mlp_bwd(W, p + "mlp.fc1", p + "mlp.fc2", g2, L["h2"], L["hpre"], L["act"], M, Gl, residual=None)
-            call("sed_ln_bwd_any", dln, L["x1"], L["mean2"], L["rstd2"], self.P(p + "norm2.weight"), 1.0, g2, 1, Gl(p + "norm2.weight"),
-                 Gl(p + "norm2.bias"), M, Dd)
-            del dln
-            # gradient images (padded heads) in the zeroed slots of `_grad_slots`; one scatter launch after the loop un-pads them
-            if trainable:
-                sink = dict(out_proj=(slots[("gwo", li)].view(Dd, Dp), G(p + "attn.out_proj.bias")), linear_pos=slots[("gwp", li)].view(Dp, Dd),
-                            in_proj=(slots[("gwi", li)].view(3 * Dp, Dd), slots[("gbi", li)]),
-                            pos_bias_u=slots[("du", li)], pos_bias_v=slots[("dv", li)])
-            else:
-                sink = dict(out_proj=(None, None), linear_pos=None, in_proj=(None, None), pos_bias_u=Z(Dp), pos_bias_v=Z(Dp))
-            self._relattn_bwd(W, p + "attn.", L, dctx, posT16, hwt, g2, sink, None, residual=g2)
-            gnew = torch.empty(B, T, Dd, dtype=F32, device=dev)
-            call("sed_ln_bwd_any", g2, L["x_in"], L["mean1"], L["rstd1"], self.P(p + "norm1.weight"), L["in_scale"], gnew.view(M, Dd), 0,
-                 Gl(p + "norm1.weight"), Gl(p + "norm1.bias"), M, Dd)
-            g = gnew
-            dctx["layers"][li] = None
-        return g
-
     def _fpool_bwd(self, W, ectx, dpooled, G, need_dx):
         if self.m.f_pool_name != "attention":
             return super()._fpool_bwd(W, ectx, dpooled, G, need_dx)
@@ -906,7 +845,8 @@ class PmamEngine(SedEngine):
         dec_train = G("decoder.encoder_blocks.0.attn.in_proj.weight") is not None
         cnn_train = G("cnn.cnn.conv0.weight") is not None
         slots, scatter = ctx["gslots"] = self._grad_slots(ctx["B"], g.device, G, dec_train, cnn_train)
-        g = self._decoder_bwd(W, ctx["dctx"], g, G, dec_train, slots)
+        ctx["dctx"]["slots"] = slots        # (`_relattn_sink` reads them)
+        g = self._decoder_bwd(W, ctx["dctx"], g, G, dec_train)
         if dec_train:
             self._join_dw()      # out_proj / in_proj gradient images were filled on the weight-gradient side stream
             if "dec" in scatter:
