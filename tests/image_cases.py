@@ -1,4 +1,4 @@
-"""Value sets, host references, shapes and restated launch arithmetic for the layout kernels at the end of csrc/gemm.hip, the family that
+"""Value sets, host references, shapes and restated launch arithmetic for the layout kernels of csrc/layout.hip, the family that
 writes every GEMM operand: sed_cast_f32_bf16, sed_transpose_to_bf16, sed_f16_to_bf16_inplace, sed_split3_f16, sed_weight_residual_f16,
 sed_weight_two_term_f8, sed_fp8_tail, sed_group_colmean(_ld), sed_weight_images (importable without a GPU: no test, no GPU code).
 tests/test_image_cases_cpu.py proves on the CPU that the references are right and that every set and shape is what it is named for;
@@ -336,27 +336,27 @@ TWO_TERM_SHAPES = [(2731, 3080), (5462, 3080)]                      # (N, K)
 
 
 def cast_launch(n):
-    """sed_cast_f32_bf16, csrc/gemm.hip:2500-2503; sed_weight_residual_f16, :2830-2832: one thread per float4."""
+    """sed_cast_f32_bf16 and sed_weight_residual_f16 (csrc/layout.hip): one thread per float4."""
     return flat_launch(n // 4, CAP_4096)
 
 
 def inplace_launch(n):
-    """sed_f16_to_bf16_inplace, csrc/gemm.hip:2932-2934: one thread per 8 halves."""
+    """sed_f16_to_bf16_inplace (csrc/layout.hip): one thread per 8 halves."""
     return flat_launch(n // 8, CAP_4096)
 
 
 def split3_launch(M, K):
-    """sed_split3_f16, csrc/gemm.hip:2912-2914: one thread per pair of columns."""
+    """sed_split3_f16 (csrc/layout.hip): one thread per pair of columns."""
     return flat_launch(M * (K // 2), CAP_4096)
 
 
 def tail_launch(M, K):
-    """sed_fp8_tail, csrc/gemm.hip:2800-2801: one thread per 8 columns."""
+    """sed_fp8_tail (csrc/layout.hip): one thread per 8 columns."""
     return flat_launch(M * (K // 8), CAP_8192)
 
 
 def two_term_launch(N, K):
-    """sed_weight_two_term_f8, csrc/gemm.hip:2822-2823: one thread per 4 columns."""
+    """sed_weight_two_term_f8 (csrc/layout.hip): one thread per 4 columns."""
     return flat_launch(N * (K // 4), CAP_8192)
 
 
@@ -372,27 +372,27 @@ def loop_cases():
 
 
 def cast_args_ok(n):
-    """csrc/gemm.hip:2499 (cast: n == 0 launches one idle workgroup), :2829 (residual: n > 0)."""
+    """Argument checks of csrc/layout.hip: sed_cast_f32_bf16 (n == 0 launches one idle workgroup) and sed_weight_residual_f16 (n > 0)."""
     return n > 0 and n % 4 == 0
 
 
 def inplace_args_ok(n):
-    """csrc/gemm.hip:2931."""
+    """Argument check of sed_f16_to_bf16_inplace (csrc/layout.hip)."""
     return n % 8 == 0
 
 
 def split3_args_ok(M, K, mode):
-    """csrc/gemm.hip:2911."""
+    """Argument check of sed_split3_f16 (csrc/layout.hip)."""
     return K % 2 == 0 and M > 0 and 0 <= mode <= 2
 
 
 def tail_args_ok(M, K, ld):
-    """csrc/gemm.hip:2799."""
+    """Argument check of sed_fp8_tail (csrc/layout.hip)."""
     return M > 0 and K % 8 == 0 and ld % 8 == 0 and ld >= K + K // 2
 
 
 def two_term_args_ok(N, K, s):
-    """csrc/gemm.hip:2821."""
+    """Argument check of sed_weight_two_term_f8 (csrc/layout.hip)."""
     return N > 0 and K % 8 == 0 and -100 <= s <= 100
 
 
@@ -408,13 +408,13 @@ def transpose_cases():
 
 
 def transpose_args_ok(R, Rpad, C, ldin, in_kind):
-    """csrc/gemm.hip:2593."""
+    """Argument check of sed_transpose_to_bf16 (csrc/layout.hip)."""
     return not (Rpad < R or in_kind < 0 or in_kind > 2 or C % 64 or Rpad % 16 or ldin % 8)
 
 
 def transpose_grid(Rpad, C):
-    """csrc/gemm.hip:2594 -> (tiles along C, tiles along R); each workgroup writes up to four 16-row segments of outT, the ones with
-    r0 + seg < Rpad (:2577)."""
+    """Grid of sed_transpose_to_bf16 (csrc/layout.hip) -> (tiles along C, tiles along R); each workgroup writes up to four 16-row segments
+    of outT, the ones with r0 + seg < Rpad (transpose_kernel)."""
     return cdiv(C, 64), cdiv(Rpad, 64)
 
 
@@ -446,12 +446,12 @@ def colmean_cases():
 
 
 def colmean_args_ok(groups, rows, K, ld, step):
-    """csrc/gemm.hip:2764."""
+    """Argument check of sed_group_colmean_ld (csrc/layout.hip)."""
     return not (groups <= 0 or rows <= 0 or K % 256 or step < 1 or ld < K or ld % 8)
 
 
 def colmean_visits(rows, step):
-    """csrc/gemm.hip:2743-2744: slice sl of 8 starts at row sl x step and strides by 8 x step -> the rows read, and nvis."""
+    """group_colmean_kernel (csrc/layout.hip): slice sl of 8 starts at row sl x step and strides by 8 x step -> the rows read, and nvis."""
     vis = sorted(r for sl in range(8) for r in range(sl * step, rows, 8 * step))
     assert vis == list(range(0, rows, step))
     return vis, cdiv(rows, step)
@@ -514,7 +514,7 @@ WIMG_R, WIMG_C = (64, 80, 208), 128
 
 
 def wimg_tiles(R, C):
-    """One workgroup per 64 x 64 tile (csrc/gemm.hip:2622-2623; the engine's descriptor table counts them the same way)."""
+    """One workgroup per 64 x 64 tile (weight_images_kernel, csrc/layout.hip; the engine's descriptor table counts them the same way)."""
     return cdiv(R, 64) * (C // 64)
 
 

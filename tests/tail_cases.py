@@ -1,4 +1,4 @@
-"""Cases, inputs, float64 references and error bounds for the kernels every training step ends in (csrc/norm_elem.hip, csrc/gemm.hip):
+"""Cases, inputs, float64 references and error bounds for the kernels every training step ends in (csrc/norm_elem.hip, csrc/layout.hip):
 sed_head_fwd / _bwd, sed_attnpool_fwd / _bwd, sed_small_linear / _bwd, sed_mlm_apply / _bwd, sed_masked_mse, sed_sed_losses and
 sed_adamw_ema.  Pure construction helpers: no tests, no GPU code, no torch.nn loss or optimizer module.  Every function works on the
 device of its arguments, so tests/test_tail_cases_cpu.py proves references and bounds on the CPU and tests/test_gpu_tail_kernels.py

@@ -1,4 +1,4 @@
-"""The cast, transpose and operand-image kernels at the end of csrc/gemm.hip, bit for bit (need an MI355X): sed_cast_f32_bf16,
+"""The cast, transpose and operand-image kernels of csrc/layout.hip, bit for bit (need an MI355X): sed_cast_f32_bf16,
 sed_transpose_to_bf16, sed_f16_to_bf16_inplace, sed_split3_f16, sed_weight_residual_f16, sed_weight_two_term_f8, sed_fp8_tail,
 sed_group_colmean(_ld), sed_weight_images.  Value sets, host references, shapes and the restated launch arithmetic: tests/image_cases.py,
 proved on the CPU by tests/test_image_cases_cpu.py.

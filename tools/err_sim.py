@@ -64,7 +64,7 @@ def lin(a, w, on, R):
 
 def ln_in(x, w, b, R):
     """The LayerNorm output as the GEMM after it sees it.  Default: f16(LayerNorm(x)) (a LayerNorm kernel writing an f16 image).
-    R["ln_fold"]: the LayerNorm folded into the GEMMs around it (csrc/gemm.hip rowpart / rowstat) -- the GEMM multiplies the f16 image of
+    R["ln_fold"]: the LayerNorm folded into the GEMMs around it (csrc/gemm_args.h rowpart / rowstat) -- the GEMM multiplies the f16 image of
     the RAW stream, statistics from the fp32 values: (f16(x) - mean(x)) rstd(x) gamma + beta; R["stream"] = "lo8": the stream itself is
     kept as f16 hi + byte lo between the blocks (hi (1 + (q - 128) 2^-18))."""
     if not R.get("ln_fold"):

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsed_hip.so")
-SOURCES = ["gemm.hip", "attention.hip", "relpos_attention.hip", "norm_elem.hip", "frontend.hip", "pmam.hip", "dasm.hip", "metrics.hip", "conformer.hip",
+SOURCES = ["gemm.hip", "gemm_tn.hip", "layout.hip", "attention.hip", "relpos_attention.hip", "norm_elem.hip", "frontend.hip", "pmam.hip", "dasm.hip", "metrics.hip", "conformer.hip",
            "fpool_transformer.hip", "fdy_cnn.hip", "grad_clip.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # -ffast-math (re-association, approximate division / sqrt) only where MFMA operand rounding dominates the error anyway: the GEMM
@@ -15,9 +15,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # clip yields a NaN weak output like the reference).
 FAST = ["-ffast-math", "-fno-finite-math-only"]
 # attention kernels: MFMA accumulators stay in (unified-file) VGPRs -- the AGPR form costs a v_accvgpr_read/write per softmax
-# operand.  The GEMM file is left to the compiler: its 128x128-per-wave kernel needs the AGPR half for its 256 accumulators.
+# operand.  The GEMM files are left to the compiler: the 128x128-per-wave kernel needs the AGPR half for its 256 accumulators.
+# (layout.hip: its casts and operand images were tuned and tested bit for bit under -ffast-math, as part of gemm.hip.)
 FILE_FLAGS = {"pmam.hip": FAST,
-              "gemm.hip": FAST, "attention.hip": FAST + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+              "gemm.hip": FAST, "gemm_tn.hip": FAST, "layout.hip": FAST, "attention.hip": FAST + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
               "relpos_attention.hip": FAST + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 

@@ -141,8 +141,8 @@ __device__ __forceinline__ void softmax_tile(f32x16_t (&st)[2], f32x16_t (&o)[2]
 #define WPE 3  // 167 VGPRs: three waves per SIMD (four would spill)
 #endif
 // Output row of query q, head h (o_mode 0: token-major [B][N][H * 64]; 1: head-major [H][B * N][64], the slab-major A operand of the
-// LayerNorm-fold proj GEMM, csrc/gemm.hip a_slab; 2: token-major rows [H * 64 f16 | H * 64 e4m3] of pitch 3 H * 64 / 2 halfs, the A operand
-// of the two-term proj GEMM with the lo product on the fp8 path, gemm.hip GemmArgs.k8) -- pointer to the head's 64 columns.
+// LayerNorm-fold proj GEMM, csrc/gemm_args.h GemmArgs.a_slab; 2: token-major rows [H * 64 f16 | H * 64 e4m3] of pitch 3 H * 64 / 2 halfs, the A operand
+// of the two-term proj GEMM with the lo product on the fp8 path, gemm_args.h GemmArgs.k8) -- pointer to the head's 64 columns.
 __device__ __forceinline__ bf16_t* attn_out_row(bf16_t* O, int o_mode, int b, int h, int q, int N, int H, int B) {
     if (o_mode == 1) return O + ((size_t)h * B * N + (size_t)b * N + q) * HD;
     const int pitch = o_mode == 2 ? H * HD + H * HD / 2 : H * HD;
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE_DMA, WP
     // accumulators are 8-byte pieces of ONE query row -- stored directly, an instruction covers 32 rows x 16 bytes; read back as 16-byte
     // chunks (lane -> row lane >> 3, chunk lane & 7) it covers 8 rows x 128 contiguous bytes, the e4m3 image (o_slab 2) 8 x 64.
     // (o_slab 1: head-major output [H][B * N][64]: a workgroup's 128 queries are one contiguous 16 KB run, and the rows are the slab-major A
-    //  operand of the LayerNorm-fold proj GEMM, csrc/gemm.hip a_slab; token-major they are 128-byte pieces 1536 bytes apart)
+    //  operand of the LayerNorm-fold proj GEMM, csrc/gemm_args.h GemmArgs.a_slab; token-major they are 128-byte pieces 1536 bytes apart)
     {
         unsigned char* ws = &lds[0][0][0] + wave * 8192;      // 32 rows x 144 bytes
         const float inv = 1.0f / l_run;

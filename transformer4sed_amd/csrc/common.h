@@ -131,7 +131,7 @@ static inline int sed_check_launch() {
 }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
-// four fp32 -> four OCP e4m3 bytes (little end first) for the fp8 lo product of the two-term GEMMs (gemm.hip GemmArgs.k8):
+// four fp32 -> four OCP e4m3 bytes (little end first) for the fp8 lo product of the two-term GEMMs (gemm_args.h GemmArgs.k8):
 // v_cvt_pk_fp8_f32 rounds to nearest even; values are clamped to +-448 first (an out-of-range input would convert to NaN).
 __device__ __forceinline__ unsigned pack4_e4m3(float a, float b, float c, float d) {
     const float lim = 448.f;

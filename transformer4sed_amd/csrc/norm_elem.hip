@@ -74,7 +74,7 @@ __device__ __forceinline__ void row_store_split3_nt(const Row& r, bf16_t* p, int
         __builtin_nontemporal_store(hi, q + 2 * (DM / 4));
     }
 }
-// rows [DM f16 | DM e4m3] (pitch 3 DM / 2 halfs): the A operand of the two-term GEMMs with the lo product on the fp8 path (gemm.hip
+// rows [DM f16 | DM e4m3] (pitch 3 DM / 2 halfs): the A operand of the two-term GEMMs with the lo product on the fp8 path (gemm_args.h
 // GemmArgs.k8); the e4m3 half is 2^-2 x the f16-ROUNDED value (what sed_fp8_tail makes from the f16 half in a pass of its own)
 __device__ __forceinline__ void row_store_f16_e4m3_nt(const Row& r, bf16_t* p, int lane) {
 #pragma unroll

@@ -173,7 +173,7 @@ class SedEngine:
         #         common to all tokens of a clip, ~2 % of an inference pass, about a third of the gain -- fc1 (the weight whose rounding
         #         matters least, and a third of the encoder's GEMM work), and every GEMM of an input below the 256^2 kernel's domain.
         # The lo product of w2, x . (W - f16(W))^T, is 2^-12 of the result: it can run on the fp8 matrix path (w2f8: e4m3 images of both
-        # factors, v_mfma_scale_f32_16x16x128_f8f6f4: half of an f16 K pass; csrc/gemm.hip GemmArgs.k8).  The activations' e4m3 images come
+        # factors, v_mfma_scale_f32_16x16x128_f8f6f4: half of an f16 K pass; csrc/gemm_args.h GemmArgs.k8).  The activations' e4m3 images come
         # out of the producing kernels (LayerNorm, attention, fc1's epilogue) in the same rows as the f16 values.  e4m3 keeps ~5 % of the lo
         # product as error, which is not free here (every posterior of the validation configuration sits within 15 % of its bound), so the
         # default takes only the GEMM that pays for it with margin to spare on both fixtures: fc2 (DESIGN.md section 2 has the measured
@@ -413,13 +413,13 @@ class SedEngine:
                 gemm_nt(xin, W[wn].w, epi, bias=b, **out)
         # No-grad f16 passes that are not scored (the teacher inside the train step, frozen encoders): LayerNorm folded into the GEMMs around
         # it -- the residual GEMM writes the f16 image of the new stream + per-row partial sums, the next GEMM consumes the RAW image against
-        # gamma-scaled weights and normalises in its epilogue (csrc/gemm.hip, GemmArgs.rowpart / rowstat).  Two passes over the stream less
+        # gamma-scaled weights and normalises in its epilogue (csrc/gemm_args.h, GemmArgs.rowpart / rowstat).  Two passes over the stream less
         # per block.  SED_LN_FOLD=0 keeps the LayerNorm kernels.
         fold_ok = self.ln_fold and not wc and M >= 1024 and not getattr(m, "lora_r", 0) and (not save or lo_f > 0)
         have_stat = False       # statistics of the current stream available (false before the first residual GEMM)
         if fold_ok:
             # between folded blocks the residual stream lives as two planes (x16f = f16 hi, which is also the consumers' A operand, + xlo:
-            # 8-bit lo) instead of fp32: a producer then moves 6 bytes per element instead of 10 (csrc/gemm.hip, GemmArgs.res_lo / out_lo)
+            # 8-bit lo) instead of fp32: a producer then moves 6 bytes per element instead of 10 (csrc/gemm_args.h, GemmArgs.res_lo / out_lo)
             # (slab-major planes are addressed through one 32-bit buffer range: a plane has to stay below 2 GiB -- M < 1.4 M tokens for the
             #  stream planes, M < 349 k for the fc1 activation; beyond that the f16 planes / the row-major activation)
             lo8 = M * D * 2 < 2 ** 31
