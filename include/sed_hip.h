@@ -384,6 +384,8 @@ int sed_weight_images(const int64_t* desc, int n_desc, int total_tiles, hipStrea
 
 /* ---------------------------------------------------------------------------------------------------------------------------
  * PMAM variant of the model path: PaSST_CNN.forward (src/models/cnn_transformer/passt_cnn.py:31-88).
+ * By source: csrc/lora.hip (sed_lora_*), csrc/cnn_branch.hip (convolution patches, column statistics, BatchNorm, ContextGating, dropout
+ * masks), csrc/dw_narrow.hip (sed_transpose_narrow, sed_small_dw), csrc/pmam.hip (the rest).
  * ------------------------------------------------------------------------------------------------------------------------- */
 /* LoRA merge W_eff = W + scaling * B A, fp32 [n_out, k_in] (src/models/lora/layers.py:120-153; r = rank, A [r, k_in], Bm [n_out, r]) */
 int sed_lora_merge(const float* W, const float* A, const float* Bm, float scaling, float* out, int n_out, int k_in, int r,

@@ -7,7 +7,7 @@ CPU and the GPU tests share (pure construction helpers; no tests here).
                z0   = (idx >> 2) + (seed ^ (site << 48)) * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03 * (site + 1)       mod 2^64
                z    = splitmix64 finaliser of z0
                keep = ((z >> 16 (idx & 3)) & 0xffff) >= thr
-`pmam_keep`  csrc/pmam.hip (dropout_mask_kernel behind sed_dropout_mask): z0 = seed + (idx // 4 + 1) * 0x9E3779B97F4A7C15, the same
+`pmam_keep`  csrc/cnn_branch.hip (dropout_mask_kernel behind sed_dropout_mask): z0 = seed + (idx // 4 + 1) * 0x9E3779B97F4A7C15, the same
              finaliser, field choice and threshold.
 
 One hash serves four consecutive elements (its four 16-bit fields), so what can go wrong without any consumer noticing is: fields that

@@ -29,6 +29,13 @@ def test_library_exports_every_declared_symbol(built):
     assert _lib.lib() is not None
 
 
+def test_every_hip_source_is_built():
+    from transformer4sed_amd import build
+    on_disk = {f for f in os.listdir(build.CSRC) if f.endswith(".hip")}
+    assert on_disk == set(build.SOURCES), f"csrc/*.hip and build.SOURCES differ: {sorted(on_disk ^ set(build.SOURCES))}"
+    assert len(build.SOURCES) == len(set(build.SOURCES))
+
+
 def test_header_cites_reference_for_every_entry():
     src = open(os.path.join(ROOT, "include", "sed_hip.h")).read()
     for token in ("passt_feature_extraction.py", "data_aug.py", "filter.py", "decoder.py", "passt.py", "transformerXL.py",

@@ -1,4 +1,4 @@
-"""Per-kernel parity tests of the PMAM entry points (csrc/pmam.hip + sed_gemm_nt_cols / sed_weight_images): every op called through
+"""Per-kernel parity tests of the PMAM entry points (csrc/pmam.hip, cnn_branch.hip, lora.hip, dw_narrow.hip + sed_gemm_nt_cols / sed_weight_images): every op called through
 the C ABI against a plain PyTorch fp32 reference of the same op (needs an MI355X)."""
 import math
 

@@ -10,8 +10,8 @@ flags=("" "-DATT_NO_XCD")
 if [ "$1" = build ]; then
   for i in "${!names[@]}"; do
     ( /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result $FF ${flags[$i]} -c transformer4sed_amd/csrc/attention.hip -o /tmp/attn_${names[$i]}.o &&
-      /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC /tmp/attn_${names[$i]}.o transformer4sed_amd/build/gemm.o transformer4sed_amd/build/relpos_attention.o \
-        transformer4sed_amd/build/norm_elem.o transformer4sed_amd/build/frontend.o transformer4sed_amd/build/pmam.o -o $V/attn_${names[$i]}.so && echo built ${names[$i]} ) &
+      /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC /tmp/attn_${names[$i]}.o $(ls transformer4sed_amd/build/*.o | grep -v '/attention\.o$') \
+        -o $V/attn_${names[$i]}.so && echo built ${names[$i]} ) &
   done
   wait
 else

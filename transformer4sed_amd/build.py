@@ -6,18 +6,19 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsed_hip.so")
-SOURCES = ["gemm.hip", "gemm_tn.hip", "layout.hip", "attention.hip", "relpos_attention.hip", "norm_elem.hip", "frontend.hip", "pmam.hip", "dasm.hip", "metrics.hip", "conformer.hip",
-           "fpool_transformer.hip", "fdy_cnn.hip", "grad_clip.hip"]
+SOURCES = ["gemm.hip", "gemm_tn.hip", "layout.hip", "attention.hip", "relpos_attention.hip", "norm_elem.hip", "frontend.hip", "pmam.hip", "cnn_branch.hip", "lora.hip", "dw_narrow.hip", "dasm.hip", "metrics.hip",
+           "conformer.hip", "fpool_transformer.hip", "fdy_cnn.hip", "grad_clip.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # -ffast-math (re-association, approximate division / sqrt) only where MFMA operand rounding dominates the error anyway: the GEMM
-# epilogues, the attention softmax and the PMAM branch (16-bit NHWC activations).  The fp32 LayerNorm / pooling / loss / optimizer
-# kernels (norm_elem.hip) and the frontend are built with IEEE semantics (NaN / inf are meaningful on those paths: a fully padded
-# clip yields a NaN weak output like the reference).
+# epilogues, the attention softmax and the PMAM branch (16-bit NHWC activations): pmam.hip and the three sources split from it, the
+# CNN branch, LoRA and the narrow weight gradients, which keep its flags.  The fp32 LayerNorm / pooling / loss / optimizer kernels
+# (norm_elem.hip) and the frontend are built with IEEE semantics (NaN / inf are meaningful on those paths: a fully padded clip yields
+# a NaN weak output like the reference).
 FAST = ["-ffast-math", "-fno-finite-math-only"]
 # attention kernels: MFMA accumulators stay in (unified-file) VGPRs -- the AGPR form costs a v_accvgpr_read/write per softmax
 # operand.  The GEMM files are left to the compiler: the 128x128-per-wave kernel needs the AGPR half for its 256 accumulators.
 # (layout.hip: its casts and operand images were tuned and tested bit for bit under -ffast-math, as part of gemm.hip.)
-FILE_FLAGS = {"pmam.hip": FAST,
+FILE_FLAGS = {"pmam.hip": FAST, "cnn_branch.hip": FAST, "lora.hip": FAST, "dw_narrow.hip": FAST,
               "gemm.hip": FAST, "gemm_tn.hip": FAST, "layout.hip": FAST, "attention.hip": FAST + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
               "relpos_attention.hip": FAST + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 

@@ -38,10 +38,18 @@ __device__ __forceinline__ bf16_t f2h(float f) { return __builtin_bit_cast(bf16_
 template <bool F16> __device__ __forceinline__ float to_f32(bf16_t h) { return F16 ? h2f(h) : bf2f(h); }
 template <bool F16> __device__ __forceinline__ bf16_t to_16(float f) { return F16 ? f2h(f) : f2bf(f); }
 template <bool F16> __device__ __forceinline__ unsigned pack2(float a, float b) { return F16 ? pack2h(a, b) : pack2bf(a, b); }
+// ... and by a runtime flag, for kernels that serve both types from one instantiation
+__device__ __forceinline__ bf16_t cvt16(float v, int f16) { return f16 ? f2h(v) : f2bf(v); }
+__device__ __forceinline__ float ld16(bf16_t v, int f16) { return f16 ? h2f(v) : bf2f(v); }
 template <bool F16> __device__ __forceinline__ f32x16_t mfma32t(s16x8_t a, s16x8_t b, f32x16_t c) {
     if (F16)
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
+}
+template <bool F16> __device__ __forceinline__ f32x4_t mfma16(s16x8_t a, s16x8_t b, f32x4_t c) {
+    if (F16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 }
 __device__ __forceinline__ f32x16_t mfma32(s16x8_t a, s16x8_t b, f32x16_t c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
@@ -130,6 +138,13 @@ static inline int sed_check_launch() {
     return e == hipSuccess ? SED_OK : -(1000 + (int)e);  // -(1000 + hipError_t): decoded by the Python binding
 }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// grid of a grid-stride kernel: one thread per unit of work, at most `cap` workgroups
+static inline int grid_for(size_t work, int threads = 256, int cap = 8192) {
+    size_t b = (work + threads - 1) / threads;
+    if (b > (size_t)cap) b = cap;
+    if (b < 1) b = 1;
+    return (int)b;
+}
 
 // four fp32 -> four OCP e4m3 bytes (little end first) for the fp8 lo product of the two-term GEMMs (gemm_args.h GemmArgs.k8):
 // v_cvt_pk_fp8_f32 rounds to nearest even; values are clamped to +-448 first (an out-of-range input would convert to NaN).

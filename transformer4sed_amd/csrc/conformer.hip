@@ -10,20 +10,18 @@
 //   * LayerNorm phase: wave = frame, 12 channels per lane.  The frame's 768 convolution outputs cross from the channel-owning threads to
 //     the frame-owning wave through LDS ([20][768] fp32 forward; the backward keeps d c for 50 frames there, 150 KB of the 160 KB).
 #include "common.h"
+#include "rows768.h"
 #include "../../include/sed_hip.h"
 
-#define DM 768
 #define KW 31
 #define HALO 15
 #define TT 20
 #define TR (TT + 2 * HALO)
 #define NWAVE (DM / 64)
-#define NV 3                    // float4 per lane per 768-wide row
 #define BWD_MAX_WG 256          // workgroups of the backward: each leaves ONE partial of every parameter gradient
 #define BWD_SLOTS (KW + 3)      // per channel: 31 taps, depthwise bias, LayerNorm weight, LayerNorm bias
 
 __device__ __forceinline__ float sigmoid_acc(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ __forceinline__ float& f4(float4& v, int c) { return reinterpret_cast<float*>(&v)[c]; }
 
 // 16-bit operand row of 768 values held 4 per lane per float4 (lane + 64 i): mode 0 bf16, 1 f16, 4 split precision [hi | lo | hi] f16
 __device__ __forceinline__ void store_operand_row(const float4* v, bf16_t* y16, size_t row, int lane, int mode) {
@@ -306,18 +304,15 @@ __global__ __launch_bounds__(256) void swish_fwd_kernel(const float* __restrict_
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
-    float4 v[NV];
+    Row v;
 #pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        v[j] = reinterpret_cast<const float4*>(h + (size_t)row * DM)[lane + 64 * j];
+    for (int j = 0; j < NV; ++j) {      // (load and Swish per float4: a row_load in front of the loop costs a register)
+        v.v[j] = reinterpret_cast<const float4*>(h + (size_t)row * DM)[lane + 64 * j];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) f4(v[j], e) = f4(v[j], e) * sigmoid_acc(f4(v[j], e));
+        for (int e = 0; e < 4; ++e) f4(v.v[j], e) = f4(v.v[j], e) * sigmoid_acc(f4(v.v[j], e));
     }
-    if (y16 != nullptr) store_operand_row(v, y16, (size_t)row, lane, mode);
-    if (y32 != nullptr) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) reinterpret_cast<float4*>(y32 + (size_t)row * DM)[lane + 64 * j] = v[j];
-    }
+    if (y16 != nullptr) store_operand_row(v.v, y16, (size_t)row, lane, mode);
+    if (y32 != nullptr) row_store(v, y32 + (size_t)row * DM, lane);
 }
 
 extern "C" int sed_swish_fwd(const float* h, void* y16, float* y32, int M, int C, int mode, hipStream_t stream) {

@@ -1,5 +1,5 @@
 // Frequency-dynamic convolution (FDY-CNN) of the PaSST_CNN branch: what a dynamic layer needs beyond the base branch's patch matrix, GEMMs,
-// BatchNorm2d, ContextGating and pooling kernels (pmam.hip).  Reference: src/models/cnn/FDY_cnn.py:7-116 (pool_dim 'freq', 4 basis kernels).
+// BatchNorm2d, ContextGating and pooling kernels (cnn_branch.hip).  Reference: src/models/cnn/FDY_cnn.py:7-116 (pool_dim 'freq', 4 basis kernels).
 //
 // A dynamic 3x3 layer is  y[b, o, h, w] = sum_k a[b, k, h] conv3x3(x; weight[k])[b, o, h, w]:  the four convolutions are ONE GEMM of the
 // patch matrix against the [4 co, 9 cin] weight image (Y4, fp32 [pixels, 4 co]); the per-frame mixing weights a come from a small attention
@@ -13,11 +13,6 @@
 
 #define FDY_TR 16          // frame rows per workgroup of the attention-head kernels
 #define FDY_K 4            // basis kernels (FDY_cnn.py:130)
-
-static inline int fdy_grid(size_t work, int threads = 256, int cap = 16384) {
-    size_t b = (work + threads - 1) / threads;
-    return (int)(b < 1 ? 1 : (b > (size_t)cap ? (size_t)cap : b));
-}
 
 // ---------------------------------------------------------------------------------------------------
 // pm[r, c] = mean over the W mel bins of X[r, w, c]     (FDY_cnn.py:97; X 16-bit NHWC [R, W, Cp], channels C.. are padding)
@@ -227,7 +222,7 @@ __global__ void fdy_mix_fwd_kernel(const float* __restrict__ Y4, int ld4, const 
 extern "C" int sed_fdy_mix_fwd(const float* Y4, int ld4, const float* att, float* Y, int ldy, int64_t M, int W, int co, hipStream_t stream) {
     (void)hipGetLastError();
     if (M <= 0 || W <= 0 || (M % W) || co <= 0 || (co % 4) || (ld4 % 4) || ld4 < FDY_K * co || (ldy % 4) || ldy < co) return SED_ERR_ARG;
-    hipLaunchKernelGGL(fdy_mix_fwd_kernel, dim3(fdy_grid((size_t)M * (ldy / 4))), dim3(256), 0, stream, Y4, ld4, att, Y, ldy, (size_t)M, W, co);
+    hipLaunchKernelGGL(fdy_mix_fwd_kernel, dim3(grid_for((size_t)M * (ldy / 4), 256, 16384)), dim3(256), 0, stream, Y4, ld4, att, Y, ldy, (size_t)M, W, co);
     return sed_check_launch();
 }
 
@@ -435,13 +430,13 @@ extern "C" int sed_fdy_attn_bwd(const float* da, const float* att, const float* 
     float* wsW = ws + Pe;
     hipLaunchKernelGGL(fdy_attn_bwd_a_kernel, dim3(nblk), dim3(256), lds, stream, da, att, u, aff, beta, W2, 1.0f / temperature, dz, part, R, hid);
     hipLaunchKernelGGL(fdy_attn_bwd_b_kernel, dim3(cdiv(P, 64)), dim3(64), 0, stream, part, nblk, hid, red, gW2, gb2, ggamma, gbeta);
-    hipLaunchKernelGGL(fdy_attn_bwd_c_kernel, dim3(fdy_grid((size_t)R * hid)), dim3(256), 0, stream, dz, u, aff, red, R, hid, batch_stats);
+    hipLaunchKernelGGL(fdy_attn_bwd_c_kernel, dim3(grid_for((size_t)R * hid, 256, 16384)), dim3(256), 0, stream, dz, u, aff, red, R, hid, batch_stats);
     if (gW1 != nullptr) {
         const int rows_per = cdiv(R, nslab);
         hipLaunchKernelGGL(fdy_attn_bwd_d_kernel, dim3(cdiv(n1, 256), nslab), dim3(256), 0, stream, dz, pm, wsW, R, H, cin, hid, rows_per);
         hipLaunchKernelGGL(fdy_attn_bwd_e_kernel, dim3(cdiv(n1, 256)), dim3(256), 0, stream, wsW, nslab, n1, gW1);
     }
-    hipLaunchKernelGGL(fdy_attn_bwd_f_kernel, dim3(fdy_grid((size_t)R * cin)), dim3(256), 0, stream, dz, W1, dpm, R, H, cin, hid);
+    hipLaunchKernelGGL(fdy_attn_bwd_f_kernel, dim3(grid_for((size_t)R * cin, 256, 16384)), dim3(256), 0, stream, dz, W1, dpm, R, H, cin, hid);
     return sed_check_launch();
 }
 
@@ -462,6 +457,6 @@ __global__ void fdy_mean_bwd_add_kernel(float* __restrict__ dX, const float* __r
 extern "C" int sed_fdy_mean_bwd_add(float* dX, const float* dpm, int64_t R, int W, int C, hipStream_t stream) {
     (void)hipGetLastError();
     if (R <= 0 || W <= 0 || C <= 0 || (C % 4)) return SED_ERR_ARG;
-    hipLaunchKernelGGL(fdy_mean_bwd_add_kernel, dim3(fdy_grid((size_t)R * W * (C / 4))), dim3(256), 0, stream, dX, dpm, (size_t)R, W, C);
+    hipLaunchKernelGGL(fdy_mean_bwd_add_kernel, dim3(grid_for((size_t)R * W * (C / 4), 256, 16384)), dim3(256), 0, stream, dX, dpm, (size_t)R, W, C);
     return sed_check_launch();
 }

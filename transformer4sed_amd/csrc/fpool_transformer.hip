@@ -10,31 +10,15 @@
 // parameter gradients are reduced in two stages of fixed order, sequences never share a reduction, so every result is bit-reproducible.
 // No kernel waits on another workgroup.
 #include "common.h"
+#include "rows768.h"
 #include "../../include/sed_hip.h"
 
-#define DM 768
-#define NV 3                    // float4 per lane per 768-wide row
 #define HD 192                  // head width
 #define NMAX 16                 // longest sequence of the short attention
 #define LD (HD + 1)             // LDS row pitch of a head slice: rows one bank apart
 #define RED_MAX_WG 256          // workgroups of a backward that reduces parameter gradients: each leaves ONE partial of every gradient
 #define ROW_WAVES 4             // waves per workgroup of the row kernels, one 768-wide row per wave at a time
 
-__device__ __forceinline__ float& f4(float4& v, int c) { return reinterpret_cast<float*>(&v)[c]; }
-__device__ __forceinline__ float f4(const float4& v, int c) { return reinterpret_cast<const float*>(&v)[c]; }
-__device__ __forceinline__ void load_row(const float* p, int lane, float4* v) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) v[i] = reinterpret_cast<const float4*>(p)[lane + 64 * i];
-}
-__device__ __forceinline__ void store_row(float* p, int lane, const float4* v) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) reinterpret_cast<float4*>(p)[lane + 64 * i] = v[i];
-}
-__device__ __forceinline__ void zero_row(float* p, int lane) {
-    const float4 z = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < NV; ++i) reinterpret_cast<float4*>(p)[lane + 64 * i] = z;
-}
 // mean and 1 / sqrt(var + eps) of a row held by one wave (two passes over the registers)
 __device__ __forceinline__ void row_stats(const float4* v, float eps, float& mu, float& rs) {
     float s = 0.f;
@@ -84,10 +68,10 @@ __device__ __forceinline__ void ln_bwd_row(float4* dy, const float4* x, float mu
 // leaves partials[wg][q][768]; reduce_partials_kernel adds the workgroups in index order into the (accumulating) destinations
 // ---------------------------------------------------------------------------------------------------
 template <int NQ>
-__device__ __forceinline__ void block_partials(float (*red)[DM], float4 (*acc)[NV], float* __restrict__ partials, int lane, int wave) {
+__device__ __forceinline__ void block_partials(float (*red)[DM], const Row* acc, float* __restrict__ partials, int lane, int wave) {
     for (int q = 0; q < NQ; ++q) {
         __syncthreads();
-        store_row(red[wave], lane, acc[q]);
+        row_store(acc[q], red[wave], lane);
         __syncthreads();
         for (int c = threadIdx.x; c < DM; c += 64 * ROW_WAVES) {
             float s = red[0][c];
@@ -124,24 +108,24 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void seq_build_fwd_kernel(const flo
     const int N = 1 + F;
     const int64_t s = row / N;
     const int j = (int)(row % N);
-    float4 v[NV];
+    Row v;
     float mu = 0.f, rs = 0.f;
     if (j == 0) {       // the tag row: linear_emb(1) = weight[:, 0] + bias, the same for every sequence
-        float4 b[NV];
-        load_row(tag_w, lane, v);
-        load_row(tag_b, lane, b);
+        Row b;
+        row_load(v, tag_w, lane);
+        row_load(b, tag_b, lane);
 #pragma unroll
-        for (int i = 0; i < NV; ++i) { v[i].x += b[i].x; v[i].y += b[i].y; v[i].z += b[i].z; v[i].w += b[i].w; }
+        for (int i = 0; i < NV; ++i) { v.v[i].x += b.v[i].x; v.v[i].y += b.v[i].y; v.v[i].z += b.v[i].z; v.v[i].w += b.v[i].w; }
     } else {
         const int64_t b = s / tp, t = s % tp;
-        float4 g[NV], bt[NV];
-        load_row(x + ((size_t)b * (2 + (size_t)F * tp) + 2 + (size_t)(j - 1) * tp + t) * DM, lane, v);
-        load_row(gamma, lane, g);
-        load_row(beta, lane, bt);
-        row_stats(v, eps, mu, rs);
-        normalise_row(v, mu, rs, g, bt);
+        Row g, bt;
+        row_load(v, x + ((size_t)b * (2 + (size_t)F * tp) + 2 + (size_t)(j - 1) * tp + t) * DM, lane);
+        row_load(g, gamma, lane);
+        row_load(bt, beta, lane);
+        row_stats(v.v, eps, mu, rs);
+        normalise_row(v.v, mu, rs, g.v, bt.v);
     }
-    store_row(xs + (size_t)row * DM, lane, v);
+    row_store(v, xs + (size_t)row * DM, lane);
     if (mean != nullptr && lane == 0) { mean[row] = mu; rstd[row] = rs; }
 }
 
@@ -153,32 +137,32 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void seq_build_bwd_kernel(const flo
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int N = 1 + F;
     const size_t Ntok = 2 + (size_t)F * tp;
-    float4 g[NV], acc[3][NV];       // dgamma, dbeta, dtag
-    load_row(gamma, lane, g);
+    Row g, acc[3];       // dgamma, dbeta, dtag
+    row_load(g, gamma, lane);
 #pragma unroll
     for (int q = 0; q < 3; ++q)
 #pragma unroll
-        for (int i = 0; i < NV; ++i) acc[q][i] = float4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < NV; ++i) acc[q].v[i] = float4{0.f, 0.f, 0.f, 0.f};
     for (int64_t row = (int64_t)blockIdx.x * ROW_WAVES + wave; row < R; row += (int64_t)gridDim.x * ROW_WAVES) {
         const int64_t s = row / N;
         const int j = (int)(row % N);
         const int64_t b = s / tp, t = s % tp;
-        float4 d[NV];
-        load_row(dxs + (size_t)row * DM, lane, d);
+        Row d;
+        row_load(d, dxs + (size_t)row * DM, lane);
         if (j == 0) {
 #pragma unroll
-            for (int i = 0; i < NV; ++i) { acc[2][i].x += d[i].x; acc[2][i].y += d[i].y; acc[2][i].z += d[i].z; acc[2][i].w += d[i].w; }
+            for (int i = 0; i < NV; ++i) { acc[2].v[i].x += d.v[i].x; acc[2].v[i].y += d.v[i].y; acc[2].v[i].z += d.v[i].z; acc[2].v[i].w += d.v[i].w; }
             if (t == 0 && dx != nullptr) {      // cls / dist rows of this clip: nothing of the pooling reads them
-                zero_row(dx + (size_t)b * Ntok * DM, lane);
-                zero_row(dx + ((size_t)b * Ntok + 1) * DM, lane);
+                row_zero(dx + (size_t)b * Ntok * DM, lane);
+                row_zero(dx + ((size_t)b * Ntok + 1) * DM, lane);
             }
             continue;
         }
         const size_t tok = (size_t)b * Ntok + 2 + (size_t)(j - 1) * tp + t;
-        float4 xv[NV];
-        load_row(x + tok * DM, lane, xv);
-        ln_bwd_row(d, xv, mean[row], rstd[row], g, acc[0], acc[1]);
-        if (dx != nullptr) store_row(dx + tok * DM, lane, d);
+        Row xv;
+        row_load(xv, x + tok * DM, lane);
+        ln_bwd_row(d.v, xv.v, mean[row], rstd[row], g.v, acc[0].v, acc[1].v);
+        if (dx != nullptr) row_store(d, dx + tok * DM, lane);
     }
     block_partials<3>(red, acc, partials, lane, wave);
 }
@@ -192,14 +176,14 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void rownorm_fwd_kernel(const float
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t s = (int64_t)blockIdx.x * ROW_WAVES + wave;
     if (s >= S) return;
-    float4 v[NV], g[NV], bt[NV];
-    load_row(xs + (size_t)s * N * DM, lane, v);
-    load_row(gamma, lane, g);
-    load_row(beta, lane, bt);
+    Row v, g, bt;
+    row_load(v, xs + (size_t)s * N * DM, lane);
+    row_load(g, gamma, lane);
+    row_load(bt, beta, lane);
     float mu, rs;
-    row_stats(v, eps, mu, rs);
-    normalise_row(v, mu, rs, g, bt);
-    store_row(pooled + (size_t)s * DM, lane, v);
+    row_stats(v.v, eps, mu, rs);
+    normalise_row(v.v, mu, rs, g.v, bt.v);
+    row_store(v, pooled + (size_t)s * DM, lane);
     if (mean != nullptr && lane == 0) { mean[s] = mu; rstd[s] = rs; }
 }
 
@@ -209,19 +193,19 @@ __global__ __launch_bounds__(64 * ROW_WAVES) void rownorm_bwd_kernel(const float
                                                                     float* __restrict__ partials, int N, int64_t S) {
     __shared__ float red[ROW_WAVES][DM];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float4 g[NV], acc[2][NV];
-    load_row(gamma, lane, g);
+    Row g, acc[2];
+    row_load(g, gamma, lane);
 #pragma unroll
     for (int q = 0; q < 2; ++q)
 #pragma unroll
-        for (int i = 0; i < NV; ++i) acc[q][i] = float4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < NV; ++i) acc[q].v[i] = float4{0.f, 0.f, 0.f, 0.f};
     for (int64_t s = (int64_t)blockIdx.x * ROW_WAVES + wave; s < S; s += (int64_t)gridDim.x * ROW_WAVES) {
-        float4 d[NV], xv[NV];
-        load_row(dpooled + (size_t)s * DM, lane, d);
-        load_row(xs + (size_t)s * N * DM, lane, xv);
-        ln_bwd_row(d, xv, mean[s], rstd[s], g, acc[0], acc[1]);
-        store_row(dxs + (size_t)s * N * DM, lane, d);
-        for (int j = 1; j < N; ++j) zero_row(dxs + ((size_t)s * N + j) * DM, lane);
+        Row d, xv;
+        row_load(d, dpooled + (size_t)s * DM, lane);
+        row_load(xv, xs + (size_t)s * N * DM, lane);
+        ln_bwd_row(d.v, xv.v, mean[s], rstd[s], g.v, acc[0].v, acc[1].v);
+        row_store(d, dxs + (size_t)s * N * DM, lane);
+        for (int j = 1; j < N; ++j) row_zero(dxs + ((size_t)s * N + j) * DM, lane);
     }
     block_partials<2>(red, acc, partials, lane, wave);
 }

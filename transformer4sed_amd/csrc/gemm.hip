@@ -445,7 +445,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(const GemmArgs g) {
         _Pragma("unroll") for (int ii = 0; ii < ((IH) == 1 ? RB - 4 : 4); ++ii)                                           \
             _Pragma("unroll") for (int jj = 0; jj < 2; ++jj) {                                                            \
                 if constexpr (F8) mfma16_f16_tied(acc[4 * (IH) + ii][2 * (JH) + jj], fb[SET][jj][ks], fa[ii][ks]);           \
-                else acc[4 * (IH) + ii][2 * (JH) + jj] = mfma16t<F16>(fb[SET][jj][ks], fa[ii][ks], acc[4 * (IH) + ii][2 * (JH) + jj]); \
+                else acc[4 * (IH) + ii][2 * (JH) + jj] = mfma16<F16>(fb[SET][jj][ks], fa[ii][ks], acc[4 * (IH) + ii][2 * (JH) + jj]); \
             }                                                                                                             \
     __builtin_amdgcn_sched_barrier(0);                                                                                    \
     __builtin_amdgcn_s_barrier();                                                                                         \

@@ -157,12 +157,7 @@ __device__ __forceinline__ void pp_stage32(unsigned char* wl, const f32x4_t (&ac
             *reinterpret_cast<float4*>(wl + (ii * 16 + l15) * V3_RS32 + (PERM ? PP_COL(j, lq) : j * 16 + 4 * lq) * 4) = make_float4(a[0], a[1], a[2], a[3]);
         }
 }
-// the MFMA of both 256^2 K loops, and the LDS pointer type of their direct-to-LDS loads
-template <bool F16> __device__ __forceinline__ f32x4_t mfma16t(s16x8_t a, s16x8_t b, f32x4_t c) {
-    if (F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
+// the LDS pointer type of the direct-to-LDS loads of both 256^2 K loops (their MFMA is common.h's mfma16)
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // ---- host ----

@@ -1,5 +1,5 @@
 // Weight-gradient GEMM in TN form for gfx950 (sed_gemm_dw_tn): the 256^2 ping-pong kernel on transposing LDS reads, its two split-K
-// reduce kernels and the host entry point.  Shares the tile constants, mfma16t, pp_stage32 / v3_st and the CU budget with the NT
+// reduce kernels and the host entry point.  Shares the tile constants, mfma16, pp_stage32 / v3_st and the CU budget with the NT
 // GEMMs (gemm_args.h); nothing else.
 #include "gemm_args.h"
 #include "../../include/sed_hip.h"
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(512) void gemm_tn_dw_kernel(const TnArgs g) {
             _Pragma("unroll") for (int ii = 0; ii < 4; ++ii) {                                                            \
                 const s16x8_t af = tn_frag(al[ii][ks], ah[ii][ks], false);                                                \
                 _Pragma("unroll") for (int jj = 0; jj < 2; ++jj)                                                          \
-                    acc[4 * (IH) + ii][2 * (JH) + jj] = mfma16t<false>(bf_[jj][ks], af, acc[4 * (IH) + ii][2 * (JH) + jj]); \
+                    acc[4 * (IH) + ii][2 * (JH) + jj] = mfma16<false>(bf_[jj][ks], af, acc[4 * (IH) + ii][2 * (JH) + jj]); \
                 if ((BIAS) && do_bias && ((4 * (IH) + ii) >> 1) == wn) {                                                  \
                     unsigned w4[4];                                                                                       \
                     __builtin_memcpy(w4, &af, 16);                                                                        \

@@ -103,11 +103,6 @@ __device__ __forceinline__ void bandT_lstore(const BandRegs& b, unsigned char* d
 //     16-key blocks are the 8 consecutive keys 32 ks + 8 g .. + 7: P^T goes from the accumulators into the B operand of the
 //     V^T P^T product without leaving the lane, its A operand is one 16-byte read of the V^T tile
 // ---------------------------------------------------------------------------------------------------
-template <bool F16> __device__ __forceinline__ f32x4_t mfma16x(s16x8_t a, s16x8_t b, f32x4_t c) {
-    if (F16)
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
 typedef __attribute__((address_space(3))) void* rp_lds_ptr_t;
 #define zero4 (f32x4_t{0.f, 0.f, 0.f, 0.f})
 
@@ -210,7 +205,7 @@ __device__ __forceinline__ void relpos_fwd_body(const bf16_t* __restrict__ Qu, c
             f32x4_t gacc = zero4;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                gacc = mfma16x<F16>(*reinterpret_cast<const s16x8_t*>(rowp + (((4 * ks + g) ^ sw) << 4)), qvf[ks], gacc);
+                gacc = mfma16<F16>(*reinterpret_cast<const s16x8_t*>(rowp + (((4 * ks + g) ^ sw) << 4)), qvf[ks], gacc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) gs[85 * c + 1 + 16 * blk + 4 * g + r] = gacc[r];
         }
@@ -222,7 +217,7 @@ __device__ __forceinline__ void relpos_fwd_body(const bf16_t* __restrict__ Qu, c
             const unsigned char* kp = lds_k + (16 * kb + c) * 128;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                st[kb] = mfma16x<F16>(*reinterpret_cast<const s16x8_t*>(kp + (((4 * ks + g) ^ swc) << 4)), quf[ks], st[kb]);
+                st[kb] = mfma16<F16>(*reinterpret_cast<const s16x8_t*>(kp + (((4 * ks + g) ^ swc) << 4)), quf[ks], st[kb]);
         }
         }
         // barrier A: every wave has read the K rows of tile t -> the prefetched K rows go to LDS
@@ -287,7 +282,7 @@ __device__ __forceinline__ void relpos_fwd_body(const bf16_t* __restrict__ Qu, c
 #pragma unroll
             for (int db = 0; db < 4; ++db) {
                 const unsigned char* rowp = lds_vt + (16 * db + c) * 128;   // (row >> 1) & 7 == swc for every 16-row block
-                o[db] = mfma16x<F16>(*reinterpret_cast<const s16x8_t*>(rowp + (((4 * ks + g) ^ swc) << 4)), pf, o[db]);
+                o[db] = mfma16<F16>(*reinterpret_cast<const s16x8_t*>(rowp + (((4 * ks + g) ^ swc) << 4)), pf, o[db]);
             }
         }
         }
@@ -591,8 +586,8 @@ __device__ __forceinline__ void relpos_bwd_dq_body(
             f32x4_t gacc[5];
 #pragma unroll
             for (int blk = 0; blk < 5; ++blk) {
-                gacc[blk] = mfma16x<SF16>(bfr[blk][0], qvf[0], zero4);
-                gacc[blk] = mfma16x<SF16>(bfr[blk][1], qvf[1], gacc[blk]);
+                gacc[blk] = mfma16<SF16>(bfr[blk][0], qvf[0], zero4);
+                gacc[blk] = mfma16<SF16>(bfr[blk][1], qvf[1], gacc[blk]);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -623,8 +618,8 @@ __device__ __forceinline__ void relpos_bwd_dq_body(
                 dp[kb] = zero4;
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
-                    st[kb] = mfma16x<SF16>(kfr[kb][ks], quf[ks], st[kb]);
-                    dp[kb] = mfma16x<false>(vfr[kb][ks], dof[ks], dp[kb]);
+                    st[kb] = mfma16<SF16>(kfr[kb][ks], quf[ks], st[kb]);
+                    dp[kb] = mfma16<false>(vfr[kb][ks], dof[ks], dp[kb]);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -701,14 +696,14 @@ __device__ __forceinline__ void relpos_bwd_dq_body(
                                          pack2bf(dp[2 * ks + 1][0], dp[2 * ks + 1][1]), pack2bf(dp[2 * ks + 1][2], dp[2 * ks + 1][3]));
             const s16x8_t dsf = __builtin_bit_cast(s16x8_t, dsu);
 #pragma unroll
-            for (int db = 0; db < 4; ++db) dqu[db] = mfma16x<false>(ktf[ks][db], dsf, dqu[db]);      // ((row >> 1) & 7 == swc for every 16-row block)
+            for (int db = 0; db < 4; ++db) dqu[db] = mfma16<false>(ktf[ks][db], dsf, dqu[db]);      // ((row >> 1) & 7 == swc for every 16-row block)
         }
         // ---- dQv^T[d, q] += P^T[d, rho] dG^T[rho, q]   (96 rho slots, the last 16 and the cells outside the band are zeros)
 #pragma unroll
         for (int ks = 0; ks < 3; ++ks) {
             const s16x8_t gf = *reinterpret_cast<const s16x8_t*>(dgl + c * 192 + 64 * ks + 16 * g);
 #pragma unroll
-            for (int db = 0; db < 4; ++db) dqv[db] = mfma16x<false>(ptf[ks][db], gf, dqv[db]);
+            for (int db = 0; db < 4; ++db) dqv[db] = mfma16<false>(ptf[ks][db], gf, dqv[db]);
         }
         if (more) {
             asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
@@ -839,8 +834,8 @@ __device__ __forceinline__ void relpos_bwd_dkdv_stream_body(const bf16_t* __rest
 #pragma unroll
             for (int db = 0; db < 4; ++db) {
                 const int ro = (16 * db + c) * 128 + (((4 * ks + g) ^ swc) << 4);
-                dk[db] = mfma16x<false>(*reinterpret_cast<const s16x8_t*>(lds[cur][0] + ro), bs[ks], dk[db]);
-                dv[db] = mfma16x<false>(*reinterpret_cast<const s16x8_t*>(lds[cur][1] + ro), bp[ks], dv[db]);
+                dk[db] = mfma16<false>(*reinterpret_cast<const s16x8_t*>(lds[cur][0] + ro), bs[ks], dk[db]);
+                dv[db] = mfma16<false>(*reinterpret_cast<const s16x8_t*>(lds[cur][1] + ro), bp[ks], dv[db]);
             }
         }
         if (t < t_hi) {

@@ -1,6 +1,7 @@
 """Forward engine of the PMAM variant (`PaSST_CNN`, src/models/cnn_transformer/passt_cnn.py:9-91).
 
-Reuses every encoder / context-network kernel of the MAT-SED engine and adds, in HIP (csrc/pmam.hip):
+Reuses every encoder / context-network kernel of the MAT-SED engine and adds, in HIP (csrc/lora.hip, cnn_branch.hip, dw_narrow.hip for
+the first two items and the narrow layers' weight gradients, csrc/pmam.hip for the rest):
   * LoRA linears (src/models/lora/layers.py:88-153): the operand image of each encoder weight is W + s B A (one merge kernel per
     weight), so the forward GEMMs are the MAT-SED ones;
   * the CNN branch (src/models/cnn/base.py:62-113): NHWC 16-bit activations, every 3x3 convolution = patch gather + one NT GEMM
