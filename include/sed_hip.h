@@ -655,6 +655,29 @@ int sed_fdy_attn_bwd(const float* da, const float* att, const float* u, const fl
 /* backward of sed_fdy_freq_mean onto the input gradient sed_col2im3x3 wrote: dX fp32 [R, W, C] += dpm [R, C] / W */
 int sed_fdy_mean_bwd_add(float* dX, const float* dpm, int64_t R, int W, int C, hipStream_t stream);
 
+/* ------------------------------------------------------------------ PMAM tokenizer: full-covariance Gaussian mixture (csrc/gmm.hip) */
+/* What recipes/desed/pmam/gmm.py and generate_pseudo_label.py take from pycave's GaussianMixture(covariance_type="full"): the densities
+ * of every frame under every component.  With Sigma_k = L_k L_k^T:  log N(x; mu_k, Sigma_k) = -0.5 (D log 2 pi + log det Sigma_k) -
+ * 0.5 |L_k^-1 (x - mu_k)|^2.
+ * sed_gmm_maha: X [N, D] fp32 (row pitch ldx >= D), P [K, D, D] fp32 with row j of P_k = row j of L_k^-1 (lower triangular; the strict
+ * upper triangle must be zero: d tiles above the diagonal are not read), b [K, D] = -P_k mu_k ->
+ *   maha[n, k] = sum_j (sum_d X[n, d] P_k[j, d] + b_k[j])^2,   maha [N, K] packed.
+ * fp32-input matrix instruction (exact fp32 products, fp32 accumulation); the whitened row is never stored; every (n, k) is written once, no
+ * atomics: the same bits in every run.  D % 32 == 0, 32 <= D <= 768, 1 <= K <= 64, N >= 1, P 16-byte aligned; otherwise SED_ERR_ARG. */
+int sed_gmm_maha(const float* X, const float* P, const float* b, float* maha, int64_t N, int D, int K, int64_t ldx, hipStream_t stream);
+/* Posteriors from maha [N, K] and logc [K] (logc_k = log pi_k - 0.5 (D log 2 pi + log det Sigma_k), host float64 rounded to fp32), scores
+ * s = logc - 0.5 maha; every output nullable: resp [N, K] = softmax_k(s) (max subtracted), logp [N] = log sum_k exp(s), argmax [N] (lowest
+ * index of the largest score), colsum_part [n_blocks, K] = per-workgroup column sums of resp (n_blocks <= 65535 = the launch's grid; the
+ * rows a workgroup adds and their order depend on (N, n_blocks) alone).  1 <= K <= 64.
+ * sed_gmm_colsum_reduce: colsum[k] (double; accumulate != 0: +=) = sum of the n_blocks partial rows in a fixed order -- N_k without atomics. */
+int sed_gmm_resp(const float* maha, const float* logc, float* resp, float* logp, int* argmax, float* colsum_part, int n_blocks, int64_t N,
+                 int K, hipStream_t stream);
+int sed_gmm_colsum_reduce(const float* colsum_part, int n_blocks, int K, double* colsum, int accumulate, hipStream_t stream);
+/* A[n, :] = sqrt(w[n w_stride]) (X[n, :] - mu) for rows 0 .. N-1: X row pitch ldx >= D, mu [D], w = one column of resp (pointer + stride),
+ * A [N, D] packed -- the operand of the M-step's covariance product A^T A (sed_gemm_f32 with transA = transB = 1).  Writes nothing else. */
+int sed_gmm_center_scale(const float* X, const float* mu, const float* w, float* A, int64_t N, int D, int64_t ldx, int64_t w_stride,
+                         hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

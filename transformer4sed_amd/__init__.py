@@ -9,3 +9,12 @@ profiles/r5_host_contention.txt).  `transformer4sed_amd.hostcpu.recommended_env(
 set it as an import side effect."""
 
 from .grad_clip import clip_grad_norm_, grad_chunk_table, grad_norms  # noqa: E402,F401  (host arithmetic + lazy imports: loads no library)
+
+_TOKENIZER = ("GaussianMixtureTokenizer", "KMeansTokenizer", "FeatureExtractor", "PseudoLabelGenerator", "save_prob")
+
+
+def __getattr__(name):      # the PMAM tokenizer (tokenizer.py), resolved on first use: it pulls in the op layer
+    if name in _TOKENIZER:
+        from . import tokenizer
+        return getattr(tokenizer, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -728,7 +728,14 @@ class SedEngine:
                 ctx["layers"].append(dict(att, x_in=cur, in_scale=in_scale, mean1=mean1, rstd1=rstd1, x1=x1, h2=h2, mean2=mean2,
                                           rstd2=rstd2, hpre=hpre, act=act))
             cur = x2
+            self._tap(li, cur)
         return cur, ctx
+
+    def _tap(self, where, value):
+        """`extract_features` (passt_sed.py): hand out the stage output it asked for.  `feature_tap` is None on every other forward."""
+        tap = getattr(self, "feature_tap", None)
+        if tap is not None and tap["layer"] == where:
+            tap["out"] = value
 
     # ------------------------------------------------------------------ context network, decoder="conformer"
     def _swish_ffn_fwd(self, W, ff, norm, xin, M, save):
@@ -799,6 +806,7 @@ class SedEngine:
                 ctx["layers"].append(dict(att, ffm=ffm, ff=ff, x1=x1, mean1=mean1, rstd1=rstd1, x2=x2, yc=yc, meanc=meanc, rstdc=rstdc, xp=xp,
                                           ys=ys, conv=conv, cmean=cmean, crstd=crstd, x4=x4, fmean=fmean, frstd=frstd))
             cur = out
+            self._tap(li, cur.view(B, T, D))
         return cur.view(B, T, D), ctx
 
     # ------------------------------------------------------------------ full forward
@@ -831,6 +839,13 @@ class SedEngine:
         Tdec = (tp + 1) * m.decode_ratio      # 99 -> 100 frames (passt_sed.py:258)
         xg, tctx = self._trunk_fwd(W, mel, pooled, tp, Tdec, opt, save)
         out["frame_before_mask"] = xg
+        if getattr(self, "feature_tap", None) is not None and self.feature_tap["layer"] == "after_interpolate":
+            # what the reference's interpolate_module hook sees: the pooled encoder features at Tdec frames, encoder width
+            x768 = xg
+            if xg.shape[-1] != D or type(self)._trunk_fwd is not SedEngine._trunk_fwd:       # (a trunk that projects before it interpolates)
+                x768 = torch.empty(B, Tdec, D, dtype=F32, device=dev)
+                call("sed_interp_fwd", pooled, x768, B, tp, 1, m.decode_ratio)
+            self._tap("after_interpolate", x768)
         dec_in = xg
         plan = mlm_plan if (m.mlm and mlm_plan is not None) else None
         if plan is not None:

@@ -579,6 +579,32 @@ class PaSST_SED(SEDModel):
             return o["mlm_pred"], other
         return o["strong"], o["weak"], other
 
+    @torch.no_grad()
+    def extract_features(self, mel, feature_layer):
+        """Frame features for the PMAM tokenizer (the forward hooks of recipes/desed/pmam/extractor_feature.py:81-104), from one
+        evaluation-mode, no-grad pass through the engine: "after_interpolate" = the pooled encoder features at the decoder's frame rate
+        [B, 1000, 768] (the reference's `interpolate_module` hook); "transformer_<k>" = the output of context block k
+        [B, 1000, decoder_dim].  The training mode of the module is restored."""
+        import re
+        mt = re.fullmatch(r"transformer_(\d+)", feature_layer)
+        if mt is not None and int(mt.group(1)) < self.decoder_layer_num:
+            layer = int(mt.group(1))
+        elif feature_layer == "after_interpolate":
+            layer = feature_layer
+        else:
+            raise ValueError(f"feature_layer must be 'after_interpolate' or 'transformer_<k>' with k < {self.decoder_layer_num}, got {feature_layer!r}")
+        was_training = self.training
+        self.eval()
+        if self.engine is None:
+            self.engine = self._make_engine()
+        tap = self.engine.feature_tap = dict(layer=layer, out=None)
+        try:
+            self.forward(mel)
+        finally:
+            self.engine.feature_tap = None
+            self.train(was_training)
+        return tap["out"]
+
     def get_feature_extractor(self):
         return self.mel_trans
 
