@@ -84,6 +84,21 @@ int sed_ap_grow(const float* old_scores, const uint8_t* old_labels, int C, int n
                 int new_cap, hipStream_t stream);
 int sed_ap_compute(const float* scores, const uint8_t* labels, int C, int N, int cap, int chunk, uint32_t* all_sorted, uint32_t* pos_sorted,
                    int* pos_cnt, unsigned long long* partial, double* ap, int* npos, hipStream_t stream);
+/* Intersection-based PSDS (Bilen et al. 2020, over all score values as in Ebbers et al. 2022): what src/evaluation_measures.py:299-341
+ * `compute_psds_from_scores` gets from sed_scores_eval, and the objective metric of recipes/desed/finetune/train.py:229-253, 370-398
+ * (csrc/psds.hip; DESIGN.md section 7b holds the definition).
+ * sed_psds_sweep: scores [B,T,C] f32, post-processed frame scores.  For every (clip, class) the threshold events in descending score
+ * order into slots [B][C][T]: ev_val (score value), ev_dtp / ev_dfp (int16 change of the clip's TP / FP count of that class once the
+ * threshold passes below the value), ev_dct (int64 change of sum_k CT_k ct_q[k]); slots past the clip's distinct values are zero events.
+ * clip_id [B]: row of each clip in the ground truth, gt_ptr [n_clips + 1] CSR into gt_cls / gt_on / gt_off (microseconds), a clip's
+ * events sorted by class, at most 256 of them.  ts_us [T + 1]: frame boundaries in microseconds; frames t < min(t_pos, n_frames[b])
+ * take part (t_pos: leading frames of positive duration; n_frames may be NULL).  dtc, gtc in (0, 1].  ct_q [C] with ev_dct, or both
+ * NULL for no cross-trigger threshold (then cttc is ignored); with them C <= 32 and cttc in (0, 1].  T <= 1024.  status[0] |= 2 for a
+ * NaN score, 8 for a clip with too many events (the caller zeroes it once). */
+int sed_psds_sweep(const float* scores, const int* clip_id, const int* n_frames, const int64_t* ts_us, int t_pos, const int* gt_ptr,
+                   const int* gt_cls, const int64_t* gt_on, const int64_t* gt_off, const int64_t* ct_q, double dtc, double gtc,
+                   double cttc, int B, int T, int C, float* ev_val, int16_t* ev_dtp, int16_t* ev_dfp, int64_t* ev_dct, int* status,
+                   hipStream_t stream);
 
 /* ------------------------------------------------------------------ GEMM family (nn.Linear / conv / autograd GEMMs) */
 /* C[M,N] = A[M,K] . B[N,K]^T, bf16 operands, fp32 accumulate, fused epilogue `epi`:

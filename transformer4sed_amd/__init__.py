@@ -13,8 +13,14 @@ from .grad_clip import clip_grad_norm_, grad_chunk_table, grad_norms  # noqa: E4
 _TOKENIZER = ("GaussianMixtureTokenizer", "KMeansTokenizer", "FeatureExtractor", "PseudoLabelGenerator", "save_prob")
 
 
-def __getattr__(name):      # the PMAM tokenizer (tokenizer.py), resolved on first use: it pulls in the op layer
+_EVALUATION = ("IntersectionPSDS", "compute_psds_from_scores")
+
+
+def __getattr__(name):      # the PMAM tokenizer (tokenizer.py) and the PSDS (evaluation.py), resolved on first use: they pull in the op layer
     if name in _TOKENIZER:
         from . import tokenizer
         return getattr(tokenizer, name)
+    if name in _EVALUATION:
+        from . import evaluation
+        return getattr(evaluation, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

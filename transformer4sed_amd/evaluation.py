@@ -329,6 +329,346 @@ class MultilabelAveragePrecision:
         return (res[idx] * w).sum()
 
 
+PSDS_MAX_FRAMES = 1024         # csrc/psds.hip: frames per clip the sweep holds in LDS
+PSDS_MAX_CLIP_EVENTS = 256     # ... and ground-truth events of one clip
+PSDS_MAX_CT_CLASSES = 32       # ... and classes together with a cross-trigger threshold
+PSDS_PADDED_CLASSES = 16       # up to here `update` keeps the sweep's padded event slots and reads nothing back
+PSDS_BLOCK_CLIPS = 2048        # ... in storage allocated for this many clips at a time (the whole split, if it is smaller)
+_PSDS_UNITS = {"second": 1.0, "minute": 60.0, "hour": 3600.0}
+
+
+def _microseconds(x):
+    """Times rounded to 6 decimals (sed_scores_eval's time_decimals), as int64 microseconds."""
+    return np.rint(np.round(np.asarray(x, dtype=np.float64), 6) * 1e6).astype(np.int64)
+
+
+def _table(x):
+    return x if isinstance(x, pd.DataFrame) else pd.read_csv(x, sep="\t")
+
+
+class IntersectionPSDS:
+    """Intersection-based polyphonic sound detection score (Bilen et al. 2020) over all score values (Ebbers et al. 2022), accumulated
+    batch by batch from the post-processed frame scores the evaluation path leaves on the device.  DESIGN.md section 7b is the
+    definition; parity with sed_scores_eval's own output is not pinned (the package is not available to compare with).
+
+    `ground_truth` / `audio_durations`: TSV path or DataFrame (filename, onset, offset, event_label / filename, duration); clips are
+    keyed by the filename's stem.  `timestamps` [T + 1]: the frame boundaries shared by all clips (`encoder._frame_to_time(arange(T + 1))`).
+    `update(scores [n, T, C] fp32 device tensor, filenames, n_frames=None)` runs `sed_psds_sweep` (one wave per clip and class) and keeps
+    the threshold events, never the scores.  With C <= 16 the events stay in the sweep's padded slots -- 8 bytes per frame and class, 16
+    with a cross-trigger threshold -- and `update` never waits for the device; with more classes the slots that change no count are
+    dropped right away, which costs one small count read-back per update.  `compute()` -> (psds, {class: single-class psds}),
+    `roc()` -> the PSD-ROC and the per-class ROCs, `counts()` -> the cumulative integer counts behind them.
+
+    Refused: T > 1024, a cross-trigger threshold together with more than 32 classes, a clip with more than 256 events
+    (NotImplementedError); thresholds outside (0, 1], a class without a ground-truth event, a clip scored twice or unknown to
+    `audio_durations`, NaN scores (at `compute`), ground-truth clips without scores (at `compute`) (ValueError)."""
+
+    def __init__(self, ground_truth, audio_durations, event_classes, timestamps, dtc_threshold, gtc_threshold, cttc_threshold=None,
+                 alpha_ct=0, alpha_st=0, max_efpr=100, unit_of_time="hour"):
+        self.event_classes = list(event_classes)
+        C = self.num_classes = len(self.event_classes)
+        if C == 0 or len(set(self.event_classes)) != C:
+            raise ValueError("event_classes must be a non-empty list of distinct names")
+        for name, v in (("dtc_threshold", dtc_threshold), ("gtc_threshold", gtc_threshold), ("cttc_threshold", cttc_threshold)):
+            if v is None and name == "cttc_threshold":
+                continue
+            if v is None or not 0.0 < float(v) <= 1.0:
+                raise ValueError(f"{name} must lie in (0, 1], got {v!r}")
+        if unit_of_time not in _PSDS_UNITS:
+            raise ValueError(f"unit_of_time must be one of {sorted(_PSDS_UNITS)}")
+        if not float(max_efpr) > 0:
+            raise ValueError("max_efpr must be positive")
+        ts = np.asarray(timestamps, dtype=np.float64)
+        if ts.ndim != 1 or ts.size < 2:
+            raise ValueError("timestamps must be [T + 1] frame boundaries")
+        T = self.num_frames = ts.size - 1
+        if T > PSDS_MAX_FRAMES:
+            raise NotImplementedError(f"IntersectionPSDS: {T} frames per clip, the HIP sweep holds at most {PSDS_MAX_FRAMES}")
+        if cttc_threshold is not None and C > PSDS_MAX_CT_CLASSES:
+            raise NotImplementedError(f"IntersectionPSDS: cttc_threshold with {C} classes (at most {PSDS_MAX_CT_CLASSES}; the "
+                                      "AudioSet recipes pass None)")
+        self.dtc, self.gtc = float(dtc_threshold), float(gtc_threshold)
+        self.cttc = None if cttc_threshold is None else float(cttc_threshold)
+        self.alpha_ct, self.alpha_st, self.max_efpr = float(alpha_ct), float(alpha_st), float(max_efpr)
+        self.unit = _PSDS_UNITS[unit_of_time]
+        self.ts_us = _microseconds(ts)
+        d = np.diff(self.ts_us)
+        if (d < 0).any():
+            raise ValueError("timestamps must not decrease")
+        self.t_pos = int(T if (d > 0).all() else np.argmin(d > 0))      # leading frames of positive duration: the ones that take part
+        if (d[self.t_pos:] > 0).any():
+            raise ValueError("a frame of zero duration lies before frames of positive duration")
+
+        dur = _table(audio_durations)
+        ids = [Path(f).stem for f in dur["filename"]]
+        if len(set(ids)) != len(ids):
+            raise ValueError("audio_durations lists a clip twice")
+        self.clip_ids = ids
+        self._clip_index = {a: i for i, a in enumerate(ids)}
+        self.data_us = int(_microseconds(dur["duration"].to_numpy()).sum())
+        if self.data_us <= 0:
+            raise ValueError("audio_durations sums to nothing")
+        gt = _table(ground_truth)
+        cls_index = {c: i for i, c in enumerate(self.event_classes)}
+        per_clip = [[] for _ in ids]
+        self._gt_clips = set()
+        on_us, off_us = _microseconds(gt["onset"].to_numpy()), _microseconds(gt["offset"].to_numpy())
+        for f, label, on, off in zip(gt["filename"], gt["event_label"], on_us.tolist(), off_us.tolist()):
+            a = Path(f).stem
+            if a not in self._clip_index:
+                raise ValueError(f"ground-truth clip {a!r} is missing from audio_durations")
+            self._gt_clips.add(a)
+            if pd.isna(label):
+                continue                                # (a clip without events)
+            if label not in cls_index:
+                raise ValueError(f"ground-truth label {label!r} is not one of event_classes")
+            if off <= on:
+                raise ValueError(f"ground-truth event of {a!r} with offset <= onset")
+            per_clip[self._clip_index[a]].append((cls_index[label], on, off))
+        ptr, flat = [0], []
+        for a, ev in zip(ids, per_clip):
+            if len(ev) > PSDS_MAX_CLIP_EVENTS:
+                raise NotImplementedError(f"IntersectionPSDS: clip {a!r} has {len(ev)} events (at most {PSDS_MAX_CLIP_EVENTS})")
+            flat += sorted(ev)
+            ptr.append(len(flat))
+        self.gt_ptr = np.asarray(ptr, dtype=np.int32)
+        self.gt = np.asarray(flat, dtype=np.int64).reshape(-1, 3)        # class, onset_us, offset_us; CSR by clip, sorted by (clip, class)
+        self.n_ref = np.bincount(self.gt[:, 0], minlength=C).astype(np.int64)
+        self.class_us = np.bincount(self.gt[:, 0], weights=(self.gt[:, 2] - self.gt[:, 1]).astype(np.float64), minlength=C).astype(np.int64)
+        if (self.n_ref == 0).any():
+            raise ValueError("event classes without a ground-truth event (pass the classes of the ground truth only): "
+                             f"{[c for c, n in zip(self.event_classes, self.n_ref) if n == 0]}")
+        # cross-trigger term as ONE integer: sum_k CT_k ct_q[k], ct_q[k] = round(w_k / ct_unit), w_k = 1 / (T_k [s] (C - 1)).  The scale
+        # leaves room for every detection of every clip (at most ceil(T / 2) per clip and class) cross-triggering every other class.
+        self.ct_q, self.ct_unit = None, 0.0
+        if self.cttc is not None:
+            w = 1e6 / self.class_us.astype(np.float64) / max(C - 1, 1) if C > 1 else np.zeros(C)
+            bound = len(ids) * ((T + 1) // 2) * max(C - 1, 1)
+            self.ct_unit = float(w.max()) / 2.0 ** (62 - int(bound).bit_length()) if C > 1 else 1.0
+            self.ct_q = np.rint(w / self.ct_unit).astype(np.int64)
+        self._dev = self._status = None                 # ground truth on the device and the sweep's status word: made at the first update
+        self._blocks = []                               # slot storage of the padded form: dict(cap, used, slots)
+        self.reset()
+
+    def reset(self):
+        """Forgets every scored clip (a new validation epoch); the ground truth stays where it is."""
+        self._seen = set()
+        self._chunks = []           # compacted events: (class int64, value f32, dTP int64, dFP int64, dCT int64 | None)
+        self._padded = []           # the sweep's slots as they are: (value [n, C, T] f32, dTP int16, dFP int16, dCT int64 | None)
+        self._points = None
+        self._blocks = self._blocks[:1]
+        for blk in self._blocks:
+            blk["used"] = 0
+        if self._status is not None:
+            self._status.zero_()
+
+    # ---- device half
+    def _constants(self, dev):
+        if self._dev is None:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            self._dev = dict(device=dev, ts=up(self.ts_us), ptr=up(self.gt_ptr), cls=up(self.gt[:, 0].astype(np.int32)),
+                             on=up(self.gt[:, 1]), off=up(self.gt[:, 2]), q=up(self.ct_q) if self.ct_q is not None else None)
+            self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        elif self._dev["device"] != dev:
+            raise ValueError(f"batches on different devices ({self._dev['device']}, {dev})")
+        return self._dev
+
+    def _sweep(self, scores, clip_index, n_frames):
+        """scores [n, T, C] fp32 on the device -> the sweep's event slots (value f32, dTP int16, dFP int16, dCT int64 | None), each
+        [n, C, T].  Stream-ordered: the clip rows travel through pinned memory, nothing is read back."""
+        if not scores.is_cuda:
+            raise RuntimeError("IntersectionPSDS needs scores on an MI355X (HIP) device; the sweep has no CPU path")
+        k = self._constants(scores.device)
+        n, T, C = scores.shape
+        host = torch.tensor([clip_index] if n_frames is None or isinstance(n_frames, torch.Tensor)
+                            else [clip_index, [int(v) for v in n_frames]], dtype=torch.int32)
+        side = host.pin_memory().to(scores.device, non_blocking=True)
+        nf = side[1] if side.shape[0] == 2 else n_frames
+        if isinstance(nf, torch.Tensor):
+            nf = nf.to(device=scores.device, dtype=torch.int32).contiguous()
+        val, dtp, dfp, dct = self._slots(n, scores.device)
+        call("sed_psds_sweep", scores, side[0], nf, k["ts"], self.t_pos, k["ptr"], k["cls"], k["on"], k["off"], k["q"], self.dtc, self.gtc,
+             self.cttc if self.cttc is not None else -1.0, n, T, C, val, dtp, dfp, dct, self._status)
+        return val, dtp, dfp, dct
+
+    def _slots(self, n, dev):
+        """Event slots for n more clips.  The padded form is kept until `compute`, so it lives in storage allocated once for the whole
+        split and reused after `reset` (no trip to the device allocator per validation step); the many-class form is compacted and
+        released right away."""
+        T, C = self.num_frames, self.num_classes
+        new = lambda rows: (torch.empty(rows, C, T, dtype=torch.float32, device=dev), torch.empty(rows, C, T, dtype=torch.int16, device=dev),
+                            torch.empty(rows, C, T, dtype=torch.int16, device=dev),
+                            torch.empty(rows, C, T, dtype=torch.int64, device=dev) if self.ct_q is not None else None)
+        if C > PSDS_PADDED_CLASSES:
+            return new(n)
+        blk = self._blocks[-1] if self._blocks else None
+        if blk is None or blk["used"] + n > blk["cap"]:
+            cap = max(n, min(len(self.clip_ids), PSDS_BLOCK_CLIPS))
+            blk = dict(cap=cap, used=0, slots=new(cap))
+            self._blocks.append(blk)
+        lo = blk["used"]
+        blk["used"] += n
+        return tuple(None if t is None else t[lo:lo + n] for t in blk["slots"])
+
+    @staticmethod
+    def _compact(val, dtp, dfp, dct):
+        keep = (dtp != 0) | (dfp != 0)
+        if dct is not None:
+            keep |= dct != 0
+        b, c, t = torch.nonzero(keep, as_tuple=True)
+        return c, val[b, c, t], dtp[b, c, t].long(), dfp[b, c, t].long(), dct[b, c, t] if dct is not None else None
+
+    def update(self, scores, filenames, n_frames=None):
+        T, C = self.num_frames, self.num_classes
+        if not isinstance(scores, torch.Tensor) or scores.dim() != 3 or tuple(scores.shape[1:]) != (T, C):
+            raise ValueError(f"scores must be a [n, {T}, {C}] tensor")
+        if scores.dtype != torch.float32:
+            raise ValueError("scores must be fp32")
+        n = scores.shape[0]
+        if len(filenames) != n or (n_frames is not None and len(n_frames) != n):
+            raise ValueError("one filename (and one n_frames entry) per clip")
+        rows, batch = [], set()
+        for f in filenames:
+            a = Path(f).stem
+            if a not in self._clip_index:
+                raise ValueError(f"clip {a!r} is missing from audio_durations")
+            if a in self._seen or a in batch:
+                raise ValueError(f"clip {a!r} was scored twice")
+            batch.add(a)
+            rows.append(self._clip_index[a])
+        if n == 0:
+            return
+        slots = self._sweep(scores.detach().contiguous(), rows, n_frames)
+        self._seen |= batch
+        self._points = None
+        if C <= PSDS_PADDED_CLASSES:
+            self._padded.append(slots)
+        else:
+            self._chunks.append(self._compact(*slots))
+
+    # ---- finish: exact integer curves, then float64 rates
+    def _check(self):
+        missing = sorted(self._gt_clips - self._seen)
+        if missing:
+            raise ValueError(f"ground-truth clips without scores: {missing}")
+        if self._status is not None:
+            status = int(self._status.item())
+            if status & 2:
+                raise ValueError("Detected NaN values in the scores")
+            if status & 8:
+                raise ValueError("a clip's ground truth exceeds the sweep's event list")
+
+    def counts(self):
+        """Per class (in event_classes order) the operating points in descending score order, cumulative and exact: dict(value f32,
+        tp, fp int64, ct int64 = sum_k CT_k ct_q[k]); events at one score value, from whatever clip or batch, are summed BEFORE the
+        point exists.  Points that change no count are left out, the empty point (nothing detected) is implied."""
+        if self._points is not None:
+            return self._points
+        self._check()
+        self._chunks += [self._compact(*s) for s in self._padded]
+        self._padded = []
+        C = self.num_classes
+        if not self._chunks or sum(ch[0].numel() for ch in self._chunks) == 0:
+            z = np.zeros(0, dtype=np.int64)
+            self._points = [dict(value=np.zeros(0, dtype=np.float32), tp=z, fp=z, ct=z) for _ in range(C)]
+            return self._points
+        has_ct = self.ct_q is not None
+        cls, val, dtp, dfp = (torch.cat([ch[i] for ch in self._chunks]) for i in range(4))
+        dct = torch.cat([ch[4] for ch in self._chunks]) if has_ct else torch.zeros_like(dtp)
+        self._chunks = [(cls, val, dtp, dfp, dct if has_ct else None)]
+        val = val + 0.0                                                     # -0.0 and +0.0 are one score value
+        order = torch.sort(val, descending=True, stable=True).indices
+        order = order[torch.sort(cls[order], stable=True).indices]        # by class, inside a class by descending value
+        cls, val, dtp, dfp, dct = cls[order], val[order], dtp[order], dfp[order], dct[order]
+        first = torch.ones_like(cls, dtype=torch.bool)
+        first[1:] = (cls[1:] != cls[:-1]) | (val[1:] != val[:-1])
+        seg = torch.cumsum(first, 0) - 1
+        n_pts = int(seg[-1]) + 1
+        pcls, pval = cls[first], val[first]
+        out = []
+        for d in (dtp, dfp, dct):
+            s = torch.zeros(n_pts, dtype=torch.int64, device=d.device).index_add_(0, seg, d)       # equal values merge here
+            tot = torch.zeros(C, dtype=torch.int64, device=d.device).index_add_(0, pcls, s)
+            out.append(torch.cumsum(s, 0) - (torch.cumsum(tot, 0) - tot)[pcls])
+        n_c = torch.bincount(pcls, minlength=C).cpu().tolist()
+        host = [x.cpu().numpy() for x in (pval, *out)]
+        self._points, lo = [], 0
+        for n in n_c:
+            v, tp, fp, ct = (x[lo:lo + n] for x in host)
+            keep = np.ones(n, dtype=bool)
+            keep[1:] = (tp[1:] != tp[:-1]) | (fp[1:] != fp[:-1]) | (ct[1:] != ct[:-1])          # merged deltas that cancelled
+            if n:
+                keep[0] = bool(tp[0] or fp[0] or ct[0])
+            self._points.append(dict(value=v[keep], tp=tp[keep], fp=fp[keep], ct=ct[keep]))
+            lo += n
+        return self._points
+
+    def _class_rocs(self):
+        """Per class the staircase (eFPR ascending, running-maximum TPR), float64, with the empty point first."""
+        rocs = []
+        for c, p in enumerate(self.counts()):
+            tpr = np.concatenate(([0.0], p["tp"].astype(np.float64) / float(self.n_ref[c])))
+            efpr = np.concatenate(([0.0], (p["fp"].astype(np.float64) / (self.data_us / 1e6)
+                                           + self.alpha_ct * (p["ct"].astype(np.float64) * self.ct_unit)) * self.unit))
+            order = np.lexsort((-tpr, efpr))                    # by eFPR; at equal eFPR the larger TPR first
+            rocs.append((efpr[order], np.maximum.accumulate(tpr[order])))
+        return rocs
+
+    @staticmethod
+    def _area(e, y, m):
+        e = np.minimum(e, m)
+        return float(np.sum(y * np.diff(np.concatenate((e, [m]))))) / m
+
+    def _psd_roc(self, rocs):
+        m = self.max_efpr
+        grid = np.unique(np.concatenate([e[e <= m] for e, _ in rocs]))
+        eff = np.empty_like(grid)
+        for lo in range(0, grid.size, 1 << 14):                 # (a [C, grid] slab at a time: 407 classes meet a long grid)
+            g = grid[lo:lo + (1 << 14)]
+            ys = np.stack([y[np.searchsorted(e, g, side="right") - 1] for e, y in rocs])
+            eff[lo:lo + g.size] = np.maximum(ys.mean(0) - self.alpha_st * ys.std(0), 0.0)
+        return grid, eff
+
+    def compute(self):
+        rocs = self._class_rocs()
+        grid, eff = self._psd_roc(rocs)
+        single = {c: self._area(e, y, self.max_efpr) for c, (e, y) in zip(self.event_classes, rocs)}
+        return self._area(grid, eff, self.max_efpr), single
+
+    def roc(self):
+        """-> ((efpr, effective tpr) of the PSD-ROC, {class: (efpr, tpr)}): staircases, each value holding up to the next eFPR."""
+        rocs = self._class_rocs()
+        grid, eff = self._psd_roc(rocs)
+        return (grid, eff), {c: r for c, r in zip(self.event_classes, rocs)}
+
+
+def compute_psds_from_scores(scores, ground_truth_file, durations_file, dtc_threshold=0.5, gtc_threshold=0.5, cttc_threshold=0.3,
+                             alpha_ct=0, alpha_st=0, max_efpr=100, num_jobs=4, save_dir=None):
+    """src/evaluation_measures.py:299-341 on `IntersectionPSDS`: `scores` is a dict audio_id -> score DataFrame as `batched_decode_preds`
+    returns them (all with the same frames and classes); they are uploaded and swept on the device.  -> (psds, single_class_psds).
+    `save_dir` writes the score tables (`write_sed_scores`); the reference's ROC plot is left out.  `num_jobs` is accepted and ignored."""
+    if not scores:
+        raise ValueError("no scores")
+    keys = list(scores)
+    first = scores[keys[0]]
+    classes = list(first.columns[2:])
+    ts = np.concatenate((first["onset"].to_numpy(), first["offset"].to_numpy()[-1:]))
+    for k in keys:
+        df = scores[k]
+        if list(df.columns[2:]) != classes or len(df) != len(first) or not np.array_equal(df["onset"].to_numpy(), ts[:-1]):
+            raise ValueError(f"score table {k!r} differs from {keys[0]!r} in classes or frames")
+    acc = IntersectionPSDS(ground_truth_file, durations_file, classes, ts, dtc_threshold, gtc_threshold, cttc_threshold, alpha_ct,
+                           alpha_st, max_efpr)
+    x = torch.from_numpy(np.stack([scores[k][classes].to_numpy(dtype=np.float32) for k in keys]))
+    dev = torch.device("cuda") if torch.cuda.is_available() else x.device     # (without a HIP device the sweep itself refuses)
+    for s in range(0, len(keys), 64):
+        acc.update(x[s:s + 64].to(dev), keys[s:s + 64])
+    res = acc.compute()
+    if save_dir is not None:
+        write_sed_scores(scores, os.path.join(save_dir, "scores"))
+    return res
+
+
 ScoreBufferTuple = namedtuple("ScoreBufferTuple", ["raw_student", "raw_teacher", "post_student", "post_teacher"])
 
 
@@ -371,8 +711,15 @@ class Evaluator:
     `write` and `flush` complete whatever is pending first, so what a caller reads is always whole.  (The synchronous form -- decode
     right behind each forward with `.cpu()` -- left the GPU idle for 14 of a 212 ms validation step, tools/ablate/step_gaps.sh.)"""
 
-    def __init__(self, net, ema_net, encoder, config):
+    PSDS_ARGS = {"psds1": dict(dtc_threshold=0.7, gtc_threshold=0.7, cttc_threshold=None, alpha_ct=0, alpha_st=1),      # train.py:229-253
+                 "psds2": dict(dtc_threshold=0.1, gtc_threshold=0.1, cttc_threshold=0.3, alpha_ct=0.5, alpha_st=1)}
+
+    def __init__(self, net, ema_net, encoder, config, ground_truth=None, audio_durations=None):
         self.net, self.ema_net, self.encoder, self.config = net, ema_net, encoder, config
+        if (ground_truth is None) != (audio_durations is None):
+            raise ValueError("ground_truth and audio_durations go together")
+        self._psds_tables = None if ground_truth is None else (_table(ground_truth), _table(audio_durations))
+        self._psds = None           # who -> {"psds1": IntersectionPSDS, "psds2": ...}, made at the first batch (it brings the frame count)
         tr = config["training"]
         self.median_filter = [int(i / 156 * 1000) for i in tr["median_window"]]          # train.py:221-227
         self.filter_type = tr.get("filter_type", "median")
@@ -396,9 +743,34 @@ class Evaluator:
             raw, post = _scores_device(strong, n, self.median_filter, self.filter_type, weak, self.weak_mask)
             job["raw"] = st.put("raw", raw)
             job["post"] = st.put("post", post) if post is not None else None
+            if self._psds_tables is not None:
+                self._psds_update(who, post if post is not None else raw, paths[:n])
         job["bin"] = st.put("bin", _events_device(strong, weak, [0.5], self.median_filter)[0])
         st.mark()
         return job
+
+    def _psds_update(self, who, scores, paths):
+        """Feeds the post-processed scores [n, frames, n_class] to the model's psds1 / psds2 accumulators: stream-ordered sweeps, the
+        host waits for nothing (10 classes: the accumulators keep the sweep's padded event slots)."""
+        if self._psds is None:
+            ts = self.encoder._frame_to_time(np.arange(scores.shape[1] + 1))
+            self._psds = {w: {k: IntersectionPSDS(*self._psds_tables, self.encoder.labels, ts, **a) for k, a in self.PSDS_ARGS.items()}
+                          for w in ("student", "teacher")}
+        for acc in self._psds[who].values():
+            acc.update(scores, paths)
+
+    def psds(self):
+        """The validation's four PSDS numbers (train.py:370-398) under the reference's log keys, and the single-class dicts under
+        "single": {"psds1/s": ..., "psds2/s": ..., "psds1/t": ..., "psds2/t": ..., "single": {same keys: {class: psds}}}."""
+        if self._psds_tables is None:
+            raise RuntimeError("Evaluator.psds() needs ground_truth= and audio_durations= at construction")
+        if self._psds is None:
+            raise RuntimeError("Evaluator.psds() called before any step")
+        out = {"single": {}}
+        for who, tag in (("student", "s"), ("teacher", "t")):
+            for k, acc in self._psds[who].items():
+                out[f"{k}/{tag}"], out["single"][f"{k}/{tag}"] = acc.compute()
+        return out
 
     # ---- host half
     def _finish(self, job):
@@ -461,8 +833,8 @@ class Evaluator:
 
 
 def mean_psds_per_type(single_psds, type_dict):
-    """passt_cnn/train.py:223-237: mean of the per-class PSDS of each class type ({"common": .., "rare": ..}), for a PSDS computed
-    elsewhere (the PSDS itself needs sed_scores_eval)."""
+    """passt_cnn/train.py:223-237: mean of the per-class PSDS of each class type ({"common": .., "rare": ..}) -- of the single-class
+    dict `IntersectionPSDS.compute` / `AudiosetStrongEvaluator.psds` return."""
     ret = {category: [] for category in set(type_dict.values())}
     for event, psds in single_psds.items():
         ret[type_dict[event]].append(psds)
@@ -495,7 +867,9 @@ class AudiosetStrongEvaluator:
 
     MODES = ("closed", "dasm", "open_vocabulary")
 
-    def __init__(self, net, encoder, config, mode, type_dict=None, events_set=None, test=False):
+    PSDS_ARGS = dict(dtc_threshold=0.7, gtc_threshold=0.7, cttc_threshold=None, alpha_ct=0, alpha_st=0)       # passt_cnn/train.py:174-186
+
+    def __init__(self, net, encoder, config, mode, type_dict=None, events_set=None, test=False, ground_truth=None, audio_durations=None):
         if mode not in self.MODES:
             raise ValueError(f"mode must be one of {self.MODES}")
         self.net, self.encoder, self.config, self.mode, self.test = net, encoder, config, mode, test
@@ -530,6 +904,32 @@ class AudiosetStrongEvaluator:
         self._stage = [_HostStage(), _HostStage()]
         self._n = 0
         self._pending = None
+        if (ground_truth is None) != (audio_durations is None):
+            raise ValueError("ground_truth and audio_durations go together")
+        self._psds_tables = None if ground_truth is None else (_table(ground_truth), _table(audio_durations))
+        self._psds = None           # IntersectionPSDS over the classes of events_set, made at the first batch
+        self._psds_cols = None
+
+    def _psds_update(self, scores, paths):
+        """Post-processed scores [n, frames, n_class] -> the PSDS accumulator, the classes outside `events_set` dropped first like
+        train.py:174-175.  With more than 16 classes each update reads one small count back (IntersectionPSDS)."""
+        if self._psds is None:
+            labels = list(self.encoder.labels)
+            keep = [i for i, l in enumerate(labels) if self.events_set is None or l in self.events_set]
+            ts = self.encoder._frame_to_time(np.arange(scores.shape[1] + 1))
+            self._psds = IntersectionPSDS(*self._psds_tables, [labels[i] for i in keep], ts, **self.PSDS_ARGS)
+            self._psds_cols = None if len(keep) == len(labels) else torch.tensor(keep, device=scores.device)
+        if self._psds_cols is not None:
+            scores = scores.index_select(2, self._psds_cols)
+        self._psds.update(scores, paths)
+
+    def psds(self):
+        """-> (psds, {class: single-class psds}) with the arguments of passt_cnn/train.py:174-186."""
+        if self._psds_tables is None:
+            raise RuntimeError("AudiosetStrongEvaluator.psds() needs ground_truth= and audio_durations= at construction")
+        if self._psds is None:
+            raise RuntimeError("AudiosetStrongEvaluator.psds() called before any step")
+        return self._psds.compute()
 
     def forward(self, feat, pad_mask):
         """-> strong [B, C, T], weak [B, C], at_out [B, C] (None for the closed set) in the encoder's class order."""
@@ -552,6 +952,8 @@ class AudiosetStrongEvaluator:
         raw, post = _scores_device(strong, n, self.median_filter, self.filter_type, None, False)
         job = {"paths": list(paths), "frames": strong.shape[-1], "stage": st, "raw": st.put("raw", raw),
                "post": st.put("post", post) if post is not None else None}
+        if self._psds_tables is not None:
+            self._psds_update(post if post is not None else raw, paths[:n])
         st.mark()
         return job
 
