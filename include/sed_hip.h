@@ -99,6 +99,22 @@ int sed_psds_sweep(const float* scores, const int* clip_id, const int* n_frames,
                    const int* gt_cls, const int64_t* gt_on, const int64_t* gt_off, const int64_t* ct_q, double dtc, double gtc,
                    double cttc, int B, int T, int C, float* ev_val, int16_t* ev_dtp, int16_t* ev_dfp, int64_t* ev_dct, int* status,
                    hipStream_t stream);
+/* Event-based (collar) and segment-based F1 counts: what src/evaluation_measures.py:52-152 (`event_based_evaluation_df`,
+ * `segment_based_evaluation_df`) and 256-295 (`log_sedeval_metrics`) get from sed_eval on the event lists of src/codec/decoder.py:15-35,
+ * logged by recipes/desed/finetune/train.py:370-398, 481-517 (csrc/event_f1.hip; DESIGN.md section 7c holds the definition).
+ * sed_event_f1_counts: one wave per (clip, class) adds n_ref, n_sys, tp, seg_tp, seg_fp, seg_fn to counts [C][6] (int64, the caller
+ * zeroes it once).  Estimated events, frame form: active [B,T,C] bytes, non-zero = on; the maximal runs a..b of every class span
+ * ts_us[a] .. ts_us[b + 1] (ts_us [T + 1], microseconds; T <= 1024).  List form (active NULL, T and ts_us ignored): est_ptr [B + 1] CSR
+ * into est_cls / est_on / est_off, a clip's events sorted by class and onset, disjoint within a class, at most 512 per clip and class.
+ * clip_id [B]: row of each clip in the ground truth, gt_ptr [n_clips + 1] CSR into gt_cls / gt_on / gt_off (microseconds), a clip's
+ * events sorted by class, at most 256 of them.  tp: maximum matching of the hits |ron - eon| <= collar_us and
+ * (double)|roff - eoff| <= max((double)collar_us, p * (double)(roff - ron)).  Segments of res_us, at most 64 per clip.  status[0] |= 1
+ * if the estimates a reference event hits are not one index interval, 4 / 8 / 16 for too many estimates / events / segments (the caller
+ * zeroes it once). */
+int sed_event_f1_counts(const uint8_t* active, const int* est_ptr, const int* est_cls, const int64_t* est_on, const int64_t* est_off,
+                        const int* clip_id, const int64_t* ts_us, const int* gt_ptr, const int* gt_cls, const int64_t* gt_on,
+                        const int64_t* gt_off, int64_t collar_us, double p, int64_t res_us, int B, int T, int C, int64_t* counts,
+                        int* status, hipStream_t stream);
 
 /* ------------------------------------------------------------------ GEMM family (nn.Linear / conv / autograd GEMMs) */
 /* C[M,N] = A[M,K] . B[N,K]^T, bf16 operands, fp32 accumulate, fused epilogue `epi`:

@@ -13,10 +13,10 @@ from .grad_clip import clip_grad_norm_, grad_chunk_table, grad_norms  # noqa: E4
 _TOKENIZER = ("GaussianMixtureTokenizer", "KMeansTokenizer", "FeatureExtractor", "PseudoLabelGenerator", "save_prob")
 
 
-_EVALUATION = ("IntersectionPSDS", "compute_psds_from_scores")
+_EVALUATION = ("IntersectionPSDS", "compute_psds_from_scores", "EventSegmentF1", "log_sedeval_metrics")
 
 
-def __getattr__(name):      # the PMAM tokenizer (tokenizer.py) and the PSDS (evaluation.py), resolved on first use: they pull in the op layer
+def __getattr__(name):      # the PMAM tokenizer (tokenizer.py), the PSDS and the F1 (evaluation.py), resolved on first use: they pull in the op layer
     if name in _TOKENIZER:
         from . import tokenizer
         return getattr(tokenizer, name)
