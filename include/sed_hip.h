@@ -709,6 +709,34 @@ int sed_gmm_colsum_reduce(const float* colsum_part, int n_blocks, int K, double*
 int sed_gmm_center_scale(const float* X, const float* mu, const float* w, float* A, int64_t N, int D, int64_t ldx, int64_t w_stride,
                          hipStream_t stream);
 
+/* ------------------------------------------------------------------ long-form detection (csrc/longform.hip) */
+/* Detection on a recording of any length: chunks of Lc samples every `hop` samples, the chunks' frame posteriors stitched into one timeline,
+ * the timeline filtered and decoded.  The reference has only an unused stub (`get_segment_scores_and_overlap_add`, src/codec/decoder.py), the
+ * definitions are DESIGN.md's.  No atomics on floats and no waiting between workgroups: the same bits in every run.
+ * sed_longform_gather: wav [L] -> out [nk, Lc], chunk j = samples (k0 + j) hop .. + Lc, zeros from sample L on; 16-byte accesses when
+ * hop, Lc and both pointers allow, scalar otherwise.  nk <= 65535. */
+int sed_longform_gather(const float* wav, float* out, int64_t L, int64_t hop, int Lc, int k0, int nk, hipStream_t stream);
+/* strong [K, C, Tc], weak [K, C] or NULL -> out [Tt, C] fp32: out[t, c] = sum_k w(t - k Hf) v_k / sum_k w(t - k Hf) over the chunks k with
+ * k Hf <= t < k Hf + Tc in ascending order, v_k = strong[k, c, t - k Hf] (x weak[k, c]: one fp32 multiply), w(i) = min(i + 1, Tc - i,
+ * max(1, Tc - Hf)); the sum in fp32, the integer denominator exact, one division.  A frame covered by ONE chunk is copied (x weak).
+ * 1 <= Hf <= Tc, 1 <= Tt <= (K - 1) Hf + Tc. */
+int sed_longform_stitch(const float* strong, const float* weak, float* out, int K, int C, int Tc, int Hf, int64_t Tt, hipStream_t stream);
+/* The filters of sed_median_filter_k (same modes 0 / 1 / 2, same element selected: bit-exact with it wherever it applies) on in / out [T, C]
+ * for any T < 2^31: tiles of 1024 frames with a halo of real neighbours, the boundary rule at the two ends of the timeline only.  sizes [C] on
+ * the device, max_size the caller's bound on them (1 .. 1024; a class whose window exceeds it comes out as NaN); modes 1 / 2 need
+ * max_size <= T. */
+int sed_longform_filter(const float* in, float* out, const int* sizes, int64_t T, int C, int mode, int max_size, hipStream_t stream);
+/* Events of post [T, C]: frame t of class c is active iff post[t, c] > th[c] (strict), every maximal run is one event.  The timeline is cut
+ * into segments of `seg` frames (nseg = ceil(T / seg) <= 65535).
+ * sed_longform_event_count: seg_counts [C nseg] (run starts per class and segment, class-major), seg_offs [C nseg + 1] their exclusive
+ * prefix sums, cls_offs [C + 1] the first row of each class (cls_offs[C] = number of events): what the host reads to allocate.
+ * sed_longform_event_write: events [n, 3] int32 rows (class, onset frame, offset frame = last active + 1), class-major, onsets ascending,
+ * from the same post / th / seg and the seg_offs of the count. */
+int sed_longform_event_count(const float* post, const float* th, int64_t T, int C, int seg, int* seg_counts, int* seg_offs, int* cls_offs,
+                             hipStream_t stream);
+int sed_longform_event_write(const float* post, const float* th, int64_t T, int C, int seg, const int* seg_offs, int* events,
+                             hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,7 @@ profiles/r5_host_contention.txt).  `transformer4sed_amd.hostcpu.recommended_env(
 set it as an import side effect."""
 
 from .grad_clip import clip_grad_norm_, grad_chunk_table, grad_norms  # noqa: E402,F401  (host arithmetic + lazy imports: loads no library)
+from .longform import LongFormDetector, chunk_plan, decode_events, median_filter_long, stitch_scores  # noqa: E402,F401  (likewise)
 
 _TOKENIZER = ("GaussianMixtureTokenizer", "KMeansTokenizer", "FeatureExtractor", "PseudoLabelGenerator", "save_prob")
 
