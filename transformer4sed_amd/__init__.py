@@ -17,7 +17,7 @@ _TOKENIZER = ("GaussianMixtureTokenizer", "KMeansTokenizer", "FeatureExtractor",
 _EVALUATION = ("IntersectionPSDS", "compute_psds_from_scores", "EventSegmentF1", "log_sedeval_metrics")
 
 
-def __getattr__(name):      # the PMAM tokenizer (tokenizer.py), the PSDS and the F1 (evaluation.py), resolved on first use: they pull in the op layer
+def __getattr__(name):      # the PMAM tokenizer (tokenizer.py), the PSDS and the F1 (evaluation/), resolved on first use: they pull in the op layer
     if name in _TOKENIZER:
         from . import tokenizer
         return getattr(tokenizer, name)

@@ -18,32 +18,12 @@
 // one IEEE product, the expression a host evaluates; ties are hits.
 //
 // Every loop is bounded by T, the clip's event count or F1_MAX_EST; there is no waiting between workgroups.
-#include "common.h"
+#include "metric_common.h"
 
 #define F1_MAX_T 1024                    // frames per clip
 #define F1_MAX_EST 512                   // estimated events of one class in one clip (1024 alternating frames make 512)
 #define F1_MAX_EV 256                    // ground-truth events of one clip
 #define F1_MAX_SEG 64                    // segments per clip: one bit each
-
-__device__ __forceinline__ int f1_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int f1_wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ unsigned long long f1_wave_or(unsigned long long v) {
-    unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo |= (unsigned)__shfl_xor((int)lo, o, 64);
-        hi |= (unsigned)__shfl_xor((int)hi, o, 64);
-    }
-    return ((unsigned long long)hi << 32) | lo;
-}
 
 // Bits of the segments on / res .. ceil(off / res) - 1 (none for a zero-length event); *over: a segment past the mask.
 __device__ __forceinline__ unsigned long long f1_segments(long long on, long long off, long long res, bool* over) {
@@ -96,7 +76,7 @@ __global__ __launch_bounds__(64) void event_f1_kernel(const uint8_t* __restrict_
         below += k < c;
         mine += k == c;
     }
-    const int c_lo = f1_wave_sum(below), n_ref = f1_wave_sum(mine);
+    const int c_lo = wave_sum_i(below), n_ref = wave_sum_i(mine);
     for (int j = lane; j < n_ref; j += 64) {
         r_on[j] = gt_on[g0 + c_lo + j];
         r_off[j] = gt_off[g0 + c_lo + j];
@@ -135,8 +115,8 @@ __global__ __launch_bounds__(64) void event_f1_kernel(const uint8_t* __restrict_
             lower += k < c;
             own += k == c;
         }
-        const int first = s0 + f1_wave_sum(lower);
-        n_sys = f1_wave_sum(own);
+        const int first = s0 + wave_sum_i(lower);
+        n_sys = wave_sum_i(own);
         for (int i = lane; i < min(n_sys, F1_MAX_EST); i += 64) {
             e_on[i] = est_on_g[first + i];
             e_off[i] = est_off_g[first + i];
@@ -171,7 +151,7 @@ __global__ __launch_bounds__(64) void event_f1_kernel(const uint8_t* __restrict_
             int best = 0x7fffffff;
             for (int j = lane; j < n_ref; j += 64)
                 if (!r_used[j] && r_lo[j] <= i && i <= r_hi[j]) best = min(best, ((int)r_hi[j] << 16) | j);
-            const int win = f1_wave_min(best);
+            const int win = wave_min_i(best);
             if (win != 0x7fffffff) {
                 const int j = win & 0xffff;
                 if ((j & 63) == lane) r_used[j] = 1;
@@ -186,8 +166,8 @@ __global__ __launch_bounds__(64) void event_f1_kernel(const uint8_t* __restrict_
     for (int j = lane; j < n_ref; j += 64) ref_m |= f1_segments(r_on[j], r_off[j], res, &over);
     for (int i = lane; i < n_sys; i += 64) sys_m |= f1_segments(e_on[i], e_off[i], res, &over);
     if (over) bits |= 16;
-    ref_m = f1_wave_or(ref_m);
-    sys_m = f1_wave_or(sys_m);
+    ref_m = wave_or_u64(ref_m);
+    sys_m = wave_or_u64(sys_m);
     if (bits) atomicOr(status, bits);
 
     // ---- stage 5

@@ -16,17 +16,11 @@
 // are sums over chunks of binary searches; with one chunk (the validation split, N = 16 901) everything stays in LDS and one launch does
 // a class.  Each term pos_ge / all_ge is rounded to a 2^-40 fixed-point integer and the terms are summed as integers: the sum does not
 // depend on the order of the clips, the chunking or the reduction tree (error <= 2^-41 per term, far below the fp32 result's rounding).
-#include "common.h"
+#include "metric_common.h"
 
 #define AP_THREADS 1024
 #define AP_MAX_CHUNK 20000               // 2 x 20000 keys = 160 000 B of LDS: the whole 160 KiB of a CU, less the static reduction slots
 #define AP_FIX 1099511627776.0           // 2^40
-
-__device__ __forceinline__ uint32_t ap_key(float f) {
-    uint32_t u = __float_as_uint(f);
-    if (u == 0x80000000u) u = 0u;        // -0.0 == +0.0: one tie
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // first index of a sorted [n] array whose key is >= k
 __device__ __forceinline__ int ap_lower_bound(const uint32_t* a, int n, uint32_t k) {
@@ -36,35 +30,6 @@ __device__ __forceinline__ int ap_lower_bound(const uint32_t* a, int n, uint32_t
         if (a[mid] < k) lo = mid + 1; else hi = mid;
     }
     return lo;
-}
-
-// Ascending bitonic sort of a[0, n) in LDS by the whole workgroup.  Every comparator puts the smaller key at the lower index (the first
-// step of each merge stage compares mirrored positions), so slots past n behave as +inf that never move: comparators reaching them are
-// skipped.
-__device__ void ap_sort(uint32_t* a, int n) {
-    int np2 = 1;
-    while (np2 < n) np2 <<= 1;
-    const int half = np2 >> 1;
-    for (int k = 2; k <= np2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int q = threadIdx.x; q < half; q += blockDim.x) {
-                int i, p;
-                if (j == (k >> 1)) {
-                    const int blk = q / j, t = q - blk * j;
-                    i = blk * k + t;
-                    p = blk * k + k - 1 - t;
-                } else {
-                    i = (q / j) * 2 * j + (q % j);
-                    p = i + j;
-                }
-                if (p < n) {
-                    const uint32_t x = a[i], y = a[p];
-                    if (x > y) { a[i] = y; a[p] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    }
 }
 
 __device__ __forceinline__ unsigned long long ap_term(int pos_ge, int all_ge) {
@@ -108,7 +73,7 @@ __global__ __launch_bounds__(AP_THREADS) void ap_sort_kernel(const float* __rest
         uint32_t k = 0;
         bool p = false;
         if (i < len) {
-            k = ap_key(sc[i]);
+            k = score_key(sc[i]);
             all[i] = k;
             p = lb[i] != 0;
         }
@@ -121,8 +86,8 @@ __global__ __launch_bounds__(AP_THREADS) void ap_sort_kernel(const float* __rest
     }
     __syncthreads();
     const int P = npos;
-    ap_sort(all, len);
-    ap_sort(pos, P);
+    lds_sort(all, len);
+    lds_sort(pos, P);
     if (nch == 1) {
         unsigned long long acc = 0;
         for (int j = threadIdx.x; j < P; j += blockDim.x) {

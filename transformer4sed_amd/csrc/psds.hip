@@ -15,45 +15,11 @@
 // ct_q the caller's fixed-point image of 1 / (T_k (C - 1)) -- integer sums do not depend on the order of clips, batches or reductions.
 //
 // Every loop is bounded by T or by the clip's event count; there is no waiting between workgroups.
-#include "common.h"
+#include "metric_common.h"
 
 #define PSDS_MAX_T 1024                  // frames per clip (the score tables have 156 .. 1000)
 #define PSDS_MAX_EV 256                  // ground-truth events of one clip held in LDS
 #define PSDS_MAX_CT_CLASSES 32           // classes with a cross-trigger threshold
-
-__device__ __forceinline__ uint32_t psds_key(float f) {
-    uint32_t u = __float_as_uint(f);
-    if (u == 0x80000000u) u = 0u;        // -0.0 == +0.0: one operating point
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// Ascending bitonic sort of a[0, n) in LDS by the workgroup, in the all-ascending form of metrics.hip's ap_sort (slots past n behave as
-// +inf that never move, so no padding is needed).
-__device__ void psds_sort(unsigned long long* a, int n) {
-    int np2 = 1;
-    while (np2 < n) np2 <<= 1;
-    const int half = np2 >> 1;
-    for (int k = 2; k <= np2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int q = threadIdx.x; q < half; q += blockDim.x) {
-                int i, p;
-                if (j == (k >> 1)) {
-                    const int blk = q / j, t = q - blk * j;
-                    i = blk * k + t;
-                    p = blk * k + k - 1 - t;
-                } else {
-                    i = (q / j) * 2 * j + (q % j);
-                    p = i + j;
-                }
-                if (p < n) {
-                    const unsigned long long x = a[i], y = a[p];
-                    if (x > y) { a[i] = y; a[p] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
 
 struct PsdsState {
     int tp, fp;
@@ -134,7 +100,7 @@ __global__ __launch_bounds__(64) void psds_sweep_kernel(const float* __restrict_
     for (int t = lane; t < tv; t += 64) {
         const float x = scores[((size_t)b * T + t) * C + c];
         nan |= x != x;
-        srt[t] = ((unsigned long long)(~psds_key(x)) << 32) | (unsigned)t;
+        srt[t] = ((unsigned long long)(~score_key(x)) << 32) | (unsigned)t;
         other[t] = -1;
     }
     for (int t = lane; t <= tv; t += 64) ts[t] = ts_us[t];
@@ -146,7 +112,7 @@ __global__ __launch_bounds__(64) void psds_sweep_kernel(const float* __restrict_
     }
     if (nan) atomicOr(status, 2);
     __syncthreads();
-    psds_sort(srt, tv);
+    lds_sort(srt, tv);
     const size_t out = ((size_t)b * C + c) * T;
     __shared__ int n_groups;
     if (lane == 0) {

@@ -89,7 +89,7 @@ def loss_function_factory(name, kwargs=None):
 
 
 class AudiosetStrongTrainer:
-    """`Trainer` of recipes/audioset_strong/base/passt_cnn/train.py (training step; the validation / test side is evaluation.py's)."""
+    """`Trainer` of recipes/audioset_strong/base/passt_cnn/train.py (training step; the validation / test side is evaluation/evaluator.py's)."""
 
     def __init__(self, net, optimizer, scheduler, config, sr=16000, ddp=None):
         self.net, self.optimizer, self.scheduler, self.config, self.sr, self.ddp = net, optimizer, scheduler, config, sr, ddp

@@ -181,15 +181,14 @@ class LongFormDetector:
         if int(batch_size) < 1:
             raise ValueError("batch_size must be positive")
         self.hop_frames, self.batch_size = int(hop_frames), int(batch_size)
+        from .evaluation.codec import check_filter_type, scaled_median_window
         tr = (config or {}).get("training", {})
         if median_filter is None and "median_window" in tr:
-            median_filter = [int(i / 156 * 1000) for i in tr["median_window"]]          # recipes/desed/finetune/train.py:221-227
+            median_filter = scaled_median_window(tr["median_window"])
         self.median_filter = None if median_filter is None else [int(s) for s in median_filter]
         if self.median_filter is not None and len(self.median_filter) != len(encoder.labels):
             raise ValueError("Length of median_filter_sizes must match the number of classes")
-        self.filter_type = filter_type if filter_type is not None else tr.get("filter_type", "median")
-        if self.filter_type not in ("median", "max"):
-            raise ValueError("filter_type must be 'median' or 'max'")
+        self.filter_type = check_filter_type(filter_type if filter_type is not None else tr.get("filter_type", "median"))
         self.weak_mask = bool(weak_mask if weak_mask is not None else tr.get("weak_mask", False))
         if forward_kwargs is None:
             forward_kwargs = config[net.get_model_name()]["val_kwargs"] if config is not None else {}
