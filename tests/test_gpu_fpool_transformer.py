@@ -606,13 +606,14 @@ def test_trainer_step_and_checkpoint(tmp_path):
 def test_mean_pool_issues_none_of_the_new_entry_points(monkeypatch):
     """A `mean_pool` model's forward (with windows) and backward launch none of the new kernels; the transformer pooling launches all six."""
     from transformer4sed_amd import engine, ops
+    from transformer4sed_amd.engine import context, encoder, grads, heads, images, pooling
     seen = []
     real = ops.call
 
     def recording(name, *args):
         seen.append(name)
         return real(name, *args)
-    for mod in (ops, engine):
+    for mod in (ops, engine, images, encoder, pooling, context, heads, grads):
         monkeypatch.setattr(mod, "call", recording)
     mel = _mel("fpooltr/launches")
     for f_pool, want in (("mean_pool", set()), (FPOOL, set(NEW_ENTRY_POINTS))):

@@ -205,7 +205,7 @@ def test_split_precision_gemm():
 
 
 def test_gemm_two_term_weights_and_row_group_bias():
-    """Evaluation-mode encoder GEMMs (engine.py `_encoder_fwd`): (a) two-term weights -- A [M, K] against [f16(W) | f16(W - f16(W))] with the
+    """Evaluation-mode encoder GEMMs (engine/encoder.py `_encoder_fwd`): (a) two-term weights -- A [M, K] against [f16(W) | f16(W - f16(W))] with the
     A panel walked twice -- are bit-identical to the ordinary GEMM over a materialised [A | A], and reproduce the fp32-weight product far
     better than the f16 weight does; (b) the row-group bias lands on the rows of its clip (ragged last tile, groups straddling tiles)."""
     from transformer4sed_amd.ops import two_term_weight

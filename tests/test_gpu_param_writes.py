@@ -1,4 +1,4 @@
-"""The derived images of the fp32 weights (engine.py `_lnf_image` / `_w2_image` / `_w2f8_image` / `_wlo_image`, the PMAM statics of
+"""The derived images of the fp32 weights (engine/images.py `_lnf_image` / `_w2_image` / `_w2f8_image` / `_wlo_image`, the PMAM statics of
 frozen LoRA blocks, DASM's folded K / V projection) are cached between forwards and rebuilt only when their key (engine.version_key)
 moves.  Every write a training script can make to the masters -- torch.optim.AdamW (foreach, for-loop, fused), trainer.FusedAdamWEMA
 (student, EMA teacher), `p.copy_` under no_grad, load_state_dict of the model / of a sub-module / through the compat
@@ -158,8 +158,8 @@ def deps(net, slot):
         norm = "norm1" if ".attn.qkv." in n else "norm2"
         return {n, n[:-len("weight")] + "bias", blk + norm + ".weight", blk + norm + ".bias"}
     if kind == "static":
-        spec = next(sp for sp in net.engine._specs[0] if sp[0] == n)
-        return {spec[1], spec[5] + ".lora_A", spec[5] + ".lora_B"}
+        spec = next(sp for sp in net.engine._specs[0] if sp.name == n)
+        return {spec.master, spec.lora + ".lora_A", spec.lora + ".lora_B"}
     L = net.dasm_head.L          # (the DASM head's fold and its split image)
     return {f"at_decoder.decoder.layers.{l}.multihead_attn.in_proj_{s}" for l in range(L) for s in ("weight", "bias")} | \
         {"at_projector.weight", "at_projector.bias"}

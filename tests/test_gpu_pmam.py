@@ -322,7 +322,7 @@ def test_pmam_finetune_stage_vs_reference(golden):
     with open("gpurun_out/pmam_errors.log", "a") as f:
         f.write("PMAM finetune-stage posterior errors (evaluation-mode weights: %s): %s\n" % ("exact", {k: f"{v:.2e}" for k, v in errs.items()}))
     # BASELINE north_star: 1e-3 on every frame posterior, the validation temperature included (sigmoid(logit / 0.5) doubles the logit
-    # error).  Measured with the evaluation-mode two-term encoder weights (engine.py `_w2_image`, the default; fc1 mean-corrected): 6.3e-4 at temp
+    # error).  Measured with the evaluation-mode two-term encoder weights (engine/images.py `_w2_image`, the default; fc1 mean-corrected): 6.3e-4 at temp
     # 0.5, 5.9e-4 / 6.3e-4 with windows; with the cheaper per-clip mean correction (SED_ENC_WCORR=mean) 7.2e-4, 7.7e-4 / 7.9e-4; with f16 weights
     # (=0) 8.9e-4 / 8.0e-4 / 8.3e-4.  The rest is per-token f16 rounding of the encoder activations, which the
     # attention pooling of this model does not average down the way MAT-SED's mean pooling does (tools/err_sim_pmam.py: the CNN branch
@@ -486,6 +486,7 @@ def test_pmam_window_forward_refuses_to_save_before_any_launch(monkeypatch):
     """No PMAM config needs the gradient through the sliding windows: forward(encoder_win=True, save=True) says so before it launches
     anything."""
     from transformer4sed_amd import engine, ops, pmam_engine
+    from transformer4sed_amd.engine import context, encoder, grads, heads, images, pooling
     net = build_ft()
     net.engine = net._make_engine()
     mel = torch.from_numpy(synth.det_uniform("pmam_ft_d2/mel", (2, 128, 1000), -1.2, 1.2)).cuda()
@@ -495,7 +496,7 @@ def test_pmam_window_forward_refuses_to_save_before_any_launch(monkeypatch):
     def recording(name, *args):
         seen.append(name)
         return real(name, *args)
-    for mod in (ops, engine, pmam_engine):
+    for mod in (ops, engine, images, encoder, pooling, context, heads, grads, pmam_engine):
         monkeypatch.setattr(mod, "call", recording)
     with pytest.raises(NotImplementedError):
         net.engine.forward(mel, encoder_win=True, save=True)

@@ -51,7 +51,8 @@ def wrap(obj, name, tag, pred=lambda *a, **k: True):
 
 wrap(ops, "h2d", "h2d")
 import transformer4sed_amd.engine as E, transformer4sed_amd.trainer as T  # noqa: E402
-for m in (E, T):
+from transformer4sed_amd.engine import encoder, heads, images  # noqa: E402
+for m in (E, images, encoder, heads, T):
     if hasattr(m, "h2d"):
         wrap(m, "h2d", "h2d")
 wrap(torch.Tensor, "copy_", "copy_", lambda self, *a, **k: self.is_cuda)

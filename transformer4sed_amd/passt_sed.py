@@ -1,5 +1,5 @@
 """`PaSST_SED` -- drop-in for the reference model class (src/models/passt/passt_sed.py:37-308) whose forward and
-backward run entirely on hand-written gfx950 kernels (engine.py).
+backward run entirely on hand-written gfx950 kernels (the engine/ package).
 
 Contract kept: constructor kwargs, forward signature and return values, accessors
 (`get_feature_extractor`, `get_model_name`, `get_backbone_upsample_ratio`, `get_backbone`), sub-module / parameter

@@ -21,7 +21,7 @@ import torch
 
 from . import ops
 
-from .engine import SedEngine, _W, ACT, D, H, version_key
+from .engine import SedEngine, ImageSpec, image_table, ACT, D, H, version_key, empty, stats
 from .ops import BF16, F16, F32, call, h2d, gemm_nt, gemm_nt_cols, gemm_dw, gemm_dw_tn, dw_tn_ok, pad64, transpose_bf16, split3, is_f16
 from .ops import EPI_F32, EPI_F32_RESID, EPI_BF16
 
@@ -83,9 +83,8 @@ class PmamEngine(SedEngine):
         return plans[key]
 
     def _image_specs(self, dev):
-        """Every 16-bit operand image of the model as (cache name, master name, R, C, plan or None, LoRA base or None, split?, kind)
-        -- kind 'act': straight image in the activation type + transposed bf16; 'bf16': straight bf16 image only -- and every padded
-        fp32 vector as (slot, master name, plan).  Shapes only: built once per device."""
+        """Every 16-bit operand image of the model as an `ImageSpec` and every padded fp32 vector as (slot, master name, plan).  Shapes
+        only: built once per device."""
         key = ("specs", str(dev))
         if getattr(self, "_specs_key", None) == key:
             return self._specs
@@ -121,7 +120,7 @@ class PmamEngine(SedEngine):
             else:
                 R = shape[0] if shape else P(master).shape[0]
                 C = P(master).numel() // R
-            mats.append((name, master, R, C, plan, lora, split, kind))
+            mats.append(ImageSpec(name, master, R, C, plan, lora, split, kind))
 
         mat("backbone.patch_embed.proj.weight", "backbone.patch_embed.proj.weight")
         for i in range(m.depth):
@@ -186,60 +185,33 @@ class PmamEngine(SedEngine):
         dev = self.P("out_norm.weight").device
         mats, vecs, geo = self._image_specs(dev)
         merged = m.lora_merged or not m.lora_r
-        sbits = int(torch.tensor(float(m.lora_scaling), dtype=torch.float32).view(torch.int32)) if m.lora_r else 0
+        lora = None if merged else (m.lora_r, int(torch.tensor(float(m.lora_scaling), dtype=torch.float32).view(torch.int32)))
         statics = self.__dict__.setdefault("_static_keys", {})
-
-        def entry(name, R, C, split, kind):
-            ent = self.cache.get(name)
-            if ent is None or ent.w.device != dev or ent.w.shape != (R, C):
-                ent = _W(torch.empty(R, C, dtype=BF16 if kind == "bf16" else ACT, device=dev),
-                         torch.empty(C, R, dtype=BF16, device=dev) if kind == "act" else None)
-                self.cache[name] = ent
-            if split and (ent.ws is None or ent.ws.device != dev):
-                ent.ws = torch.empty(R, 3 * C, dtype=F16, device=dev)
-            return ent
-
-        def row(spec, tiles):
-            name, master, R, C, plan, lora, split, kind = spec
-            ent = entry(name, R, C, split, kind)
-            use_lora = lora is not None and not merged
-            return [self.P(master).data_ptr(), ent.wt.data_ptr() if (kind == "act" and need_t) else 0, ent.w.data_ptr(),
-                    ent.ws.data_ptr() if split else 0, R, C, 2 if kind == "act" else 0, tiles,
-                    plan[0].data_ptr() if plan is not None else 0, plan[1].data_ptr() if plan is not None else 0,
-                    self.P(lora + ".lora_A").data_ptr() if use_lora else 0, self.P(lora + ".lora_B").data_ptr() if use_lora else 0,
-                    m.lora_r if use_lora else 0, sbits if use_lora else 0, 0, 0]
-
         # Frozen operands (the blocks below `freeze_layer`, cnn_trans/setting.py:66-82) keep their images across steps.  A tensor without
         # requires_grad is not necessarily constant (the EMA teacher's masters, load_state_dict, p.copy_): like every cached weight image,
         # a block's statics are rebuilt iff the storage or the version of one of its masters moved (engine.version_key).
         live, stale = [], []
-        for spec in mats:
-            name, master, R, C, plan, lora, split, kind = spec
-            if not (name.startswith("backbone.blocks.") and lora is not None):
-                live.append(spec)
+        for sp in mats:
+            if not (sp.name.startswith("backbone.blocks.") and sp.lora is not None):
+                live.append(sp)
                 continue
-            parts = [self.P(master), self.P(lora + ".lora_A"), self.P(lora + ".lora_B")]
+            parts = [self.P(sp.master), self.P(sp.lora + ".lora_A"), self.P(sp.lora + ".lora_B")]
             if any(p.requires_grad for p in parts):
-                live.append(spec)
+                live.append(sp)
                 continue
             key = version_key(parts, (merged, bool(need_t)))
-            if statics.get(name) != key or name not in self.cache:
-                stale.append(spec)
-                statics[name] = key
+            if statics.get(sp.name) != key or sp.name not in self.cache:
+                stale.append(sp)
+                statics[sp.name] = key
         for specs, cached in ((stale, False), (live, True)):
             if not specs:
                 continue
-            ptrs = tuple(self.P(sp[1]).data_ptr() for sp in specs) + tuple(self.P(sp[5] + ".lora_A").data_ptr() for sp in specs if sp[5]) + \
+            ptrs = tuple(self.P(sp.master).data_ptr() for sp in specs) + tuple(self.P(sp.lora + ".lora_A").data_ptr() for sp in specs if sp.lora) + \
                 (bool(need_t), merged, len(specs))
             if cached and getattr(self, "_wimg_key", None) == ptrs:
                 desc, n, tiles = self._wimg_desc
             else:
-                rows_, tiles = [], 0
-                for sp in specs:
-                    if sp[2] % 16 or sp[3] % 64 or not self.P(sp[1]).is_contiguous():
-                        raise RuntimeError(f"weight {sp[0]}: unsupported shape / layout for the operand images")
-                    rows_.append(row(sp, tiles))
-                    tiles += ((sp[2] + 63) // 64) * (sp[3] // 64)
+                rows_, tiles = image_table(specs, self.P, self.cache, need_t, lora)
                 desc, n = h2d(rows_, torch.int64, dev), len(rows_)
                 if cached:
                     self._wimg_desc, self._wimg_key = (desc, n, tiles), ptrs
@@ -274,17 +246,12 @@ class PmamEngine(SedEngine):
         dev = x.device
         N = 2 + 12 * tp
         M = Bx * N
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        E = empty(dev)
         pre = "f_pool_module."
         h16 = E(M, D, dt=ACT)
-        pm, pr = (E(M), E(M)) if save else (None, None)
+        pm, pr = stats(E, M, save)
         call("sed_layernorm_fwd", x, self.P("out_norm.weight"), self.P("out_norm.bias"), 1e-5, 1.0, h16, None, pm, pr, M, D, 1)
-        win = self.P(pre + "frequency_att.in_proj_weight")
-        bin_ = self.P(pre + "frequency_att.in_proj_bias")
-        q = E(1, D)
-        call("sed_small_linear", self.P(pre + "f_att_token").reshape(1, D), win[:D], bin_[:D], q, 1, D, D, 0)
-        kv16 = E(M, 2 * D, dt=ACT)
-        gemm_nt(h16, W[pre + "frequency_att.in_proj_weight"].w[D:], EPI_BF16, bias=bin_[D:], outH=kv16)
+        q, kv16 = self._token_query_fwd(W, pre, h16)
         att16 = E(Bx * tp, D, dt=ACT)
         probs = E(Bx * tp, 6, 12) if save else None
         call("sed_fpool_attn_fwd", kv16, q, att16, None, probs, Bx, N, tp, 1)
@@ -302,7 +269,7 @@ class PmamEngine(SedEngine):
         m = self.m
         dev = mel.device
         B, _, T = mel.shape
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        E = empty(dev)
         Hc, Wc = T, 128
         X = None
         layers = []
@@ -410,7 +377,7 @@ class PmamEngine(SedEngine):
         dev = col.device
         co, cin, hid, ld4 = aux["co"], aux["cin"], aux["hid"], aux["ld4"]
         R, Mi = B * Hc, B * Hc * Wc
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        E = empty(dev)
         pre = f"cnn.cnn.conv{i}.attention."
         pm, u, aff1, att = E(R, cin), E(R, hid), E(3, hid), E(R, 4)
         call("sed_fdy_freq_mean", X, is_f16(X), pm, R, Wc, cin, X.shape[-1])
@@ -434,7 +401,7 @@ class PmamEngine(SedEngine):
         co, cin, hid, ld4, ldg4, Kp = aux["co"], aux["cin"], aux["hid"], aux["ld4"], aux["ldg4"], aux["Kp"]
         Hc, Wc, D = L["H"], L["W"], L["dyn"]
         R, Mi = B * Hc, B * Hc * Wc
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        E = empty(dev)
         pre = f"cnn.cnn.conv{i}.attention."
         dY4, da = E(Mi, ldg4, dt=BF16), E(R, 4)
         call("sed_fdy_mix_bwd", dY16, dY16.shape[1], D["Y4"], ld4, D["att"], dY4, ldg4, da, R, Wc, co)
@@ -513,7 +480,7 @@ class PmamEngine(SedEngine):
         m = self.m
         dev = mel.device
         B, Dd = mel.shape[0], m.decoder_dim
-        E = lambda *s: torch.empty(*s, dtype=F32, device=dev)
+        E = empty(dev)
         feat, cctx = self._cnn_fwd(W, mel, train=m.training, save=save, drop_masks=opt["drop_masks"])
         Tc = cctx["Tc"]
         P2 = self._project(W, "cnn_projector", feat, B * Tc)
@@ -533,7 +500,7 @@ class PmamEngine(SedEngine):
         nam = None
         if getattr(m, "dasm_head", None) is not None:
             xn = E(B, Tdec, Dd)
-            nm_, nr_ = (E(B * Tdec), E(B * Tdec)) if save else (None, None)
+            nm_, nr_ = stats(E, B * Tdec, save)
             call("sed_layernorm_fwd", xg.view(B * Tdec, Dd), self.P("norm_after_merge.weight"), self.P("norm_after_merge.bias"), 1e-5, 1.0,
                  None, xn.view(B * Tdec, Dd), nm_, nr_, B * Tdec, Dd, 0)
             if save:
@@ -570,7 +537,7 @@ class PmamEngine(SedEngine):
         products are unchanged)."""
         B, Tdec, Dd = xd.shape
         C, dev = self.m.class_num, xd.device
-        E = lambda *s: torch.empty(*s, dtype=F32, device=dev)
+        E = empty(dev)
         xd_pad = torch.zeros(B, Tdec, D, dtype=F32, device=dev)
         xd_pad[:, :, :Dd] = xd
         w_pad = torch.zeros(C, D, dtype=F32, device=dev)
@@ -730,7 +697,7 @@ class PmamEngine(SedEngine):
     def _cnn_bwd(self, W, cctx, dfeat, B, G, slots):
         m = self.m
         dev = dfeat.device
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
+        E = empty(dev)
         dout = dfeat
         for i in range(len(self.cnn_aux) - 1, -1, -1):
             aux, L = self.cnn_aux[i], cctx["layers"][i]
@@ -789,26 +756,16 @@ class PmamEngine(SedEngine):
         dev = dpooled.device
         B, N, tp = ectx["B"], ectx["N"], ectx["tp"]
         M = B * N
-        E = lambda *s, dt=F32: torch.empty(*s, dtype=dt, device=dev)
-        Z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=dev)
+        E = empty(dev)
         pre = "f_pool_module."
-        train = G(pre + "frequency_att.out_proj.weight") is not None
-        g16 = self._dw_accum(dpooled, ectx["pool_att16"], B * tp, G(pre + "frequency_att.out_proj.weight"),
-                             G(pre + "frequency_att.out_proj.bias"))
+        gw = G(pre + "frequency_att.out_proj.weight")
+        g16 = self._dw_accum(dpooled, ectx["pool_att16"], B * tp, gw, G(pre + "frequency_att.out_proj.bias"))
         datt = E(B * tp, D)
         gemm_nt(g16, W[pre + "frequency_att.out_proj.weight"].wt, EPI_F32, outF=datt)
         dkv = E(M, 2 * D, dt=BF16)
-        dq = Z(1, D)
+        dq = torch.zeros(1, D, dtype=F32, device=dev)
         call("sed_fpool_attn_bwd", ectx["pool_kv16"], ectx["pool_q"], ectx["pool_probs"], datt, dkv, dq, B, N, tp, is_f16(ectx["pool_kv16"]))
-        win = self.P(pre + "frequency_att.in_proj_weight")
-        if train:
-            gin, gib = G(pre + "frequency_att.in_proj_weight"), G(pre + "frequency_att.in_proj_bias")
-            dtok = Z(1, D)
-            call("sed_small_linear_bwd", self.P(pre + "f_att_token").reshape(1, D), win[:D], None, dq, dtok, gin[:D], gib[:D], 1, D, D, 0)
-            G(pre + "f_att_token").view(1, D).add_(dtok)
-            self._dw_accum(dkv, ectx["pool_h16"], M, gin[D:], gib[D:])
-        dh = E(M, D)
-        gemm_nt(dkv, W[pre + "frequency_att.in_proj_weight"].wt[:, D:].contiguous(), EPI_F32, outF=dh)
+        dh = self._token_query_bwd(W, pre, ectx["pool_h16"], dq, dkv, G, train=gw is not None)
         gpool = E(B, N, D)
         call("sed_layernorm_bwd", dh, ectx["pool_x"], ectx["pool_mean"], ectx["pool_rstd"], self.P("out_norm.weight"), 1.0,
              gpool.view(M, D), 0, G("out_norm.weight"), G("out_norm.bias"), M, D)
@@ -860,7 +817,7 @@ class PmamEngine(SedEngine):
         B, Tdec, tp = ctx["B"], ctx["Tdec"], ctx["tp"]
         Dd = m.decoder_dim
         M = B * Tdec
-        E = lambda *s: torch.empty(*s, dtype=F32, device=g.device)
+        E = empty(g.device)
         slots, scatter = ctx["gslots"]
         if ctx.get("nam") is not None:
             nam = ctx["nam"]
