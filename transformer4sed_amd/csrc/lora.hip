@@ -46,7 +46,9 @@ __global__ __launch_bounds__(256) void lora_grad_kernel(const float* __restrict_
         // (wide rows, k_in > 1024: the four waves of a block share ONE row, a quarter of its columns each)
         __shared__ float part[4][16];
         const bool wide = k_in > 1024;
-        const int kq = wide ? ((k_in / 4 + 63) / 64) * 64 : k_in, kb = wide ? wave * kq : 0, ke = wide ? (kb + kq < k_in ? kb + kq : k_in) : k_in;
+        // (the quarter is a fourth of k_in rounded UP: from k_in / 4 rounded down, four quarters stop short of k_in whenever k_in / 4 is a
+        //  multiple of 64 and k_in % 4 != 0 -- columns 1024.. of k_in = 1025 reached no sum)
+        const int kq = wide ? (((k_in + 3) / 4 + 63) / 64) * 64 : k_in, kb = wide ? wave * kq : 0, ke = wide ? (kb + kq < k_in ? kb + kq : k_in) : k_in;
         for (int n = wide ? blockIdx.x : blockIdx.x * 4 + wave; n < n_out; n += wide ? gridDim.x : gridDim.x * 4) {
             float acc[16];
 #pragma unroll
