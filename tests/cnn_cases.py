@@ -4,7 +4,7 @@ crosses the threshold it is named for, that every drop condition holds and that 
 holds the hardware to them.
 
 A. every layer geometry of the real stack (synth.PMAM_FILTERS / PMAM_POOLING) at T = 12, B = 2, with the arguments PmamEngine passes
-   (pmam_engine.py:299-368, 697-750): LAYERS.
+   (`PmamEngine._cnn_fwd` / `_cnn_bwd`): LAYERS.
 B. the smallest shape at which each entry point's grid-stride loop (or slab loop) takes a second trip: the *_B cases.
 
 Bounds (all taken from the project, none tuned to a kernel):
@@ -48,7 +48,8 @@ Layer = collections.namedtuple("Layer", "i cin co H W ph pw Np Kp Cp ldy ldg cpi
 
 
 def layers(T=T_A):
-    """The geometry of pmam_engine.py:152-171 (Np, Kp, Cp, ldg) and :299-368 (ldy, the im2col channel pitch, H and W per layer)."""
+    """The geometry of `pmam_engine.geometry.cnn_geometry` (Np, Kp, Cp, ldg) and `cnn_layer_plans` (ldy, the im2col channel pitch, H and
+    W per layer), restated on purpose: tests/test_pmam_geometry_cpu.py holds the two to each other."""
     out, H, W, cin = [], T, 128, 1
     n = len(synth.PMAM_FILTERS)
     for i, (co, (ph, pw)) in enumerate(zip(synth.PMAM_FILTERS, synth.PMAM_POOLING)):

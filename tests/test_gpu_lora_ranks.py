@@ -1,4 +1,4 @@
-"""The engine's two LoRA gradient routes at ranks other than 8 (PmamEngine._enc_layer_bwd / _dw_accum, pmam_engine.py): the skinny
+"""The engine's two LoRA gradient routes at ranks other than 8 (PmamEngine._enc_layer_bwd / _dw_accum, pmam_engine/grads.py): the skinny
 products (sed_lora_rowproj + sed_lora_colreduce, r <= 8) and the full-dW scratch that sed_lora_grad projects after the side-stream join
 (`lora_skinny` False, or r > 8).  Depth 2, B 2, dropout 0, only the LoRA factors of the encoder trainable, the draws of the pmam_d2 golden.
 

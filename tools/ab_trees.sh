@@ -3,7 +3,7 @@
 # Without modes: three pairs of finetune2, two of pretrain and of finetune1.  With modes (any of bench.py --mode): three pairs of each.
 # Every bench run has its own time limit; the first one that fails or runs into it ends the script (nothing more is started on the GPU).
 set -o pipefail
-run() { (cd "$1" && timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 10 --mode "$2" 2>/dev/null | tail -1 | python -c "import sys, json; d = json.loads(sys.stdin.read()); r = d.get('roofline') or {}; print(d['value'], 'clips/s', d['ms_per_step'], 'ms  GEMM family', r.get('achieved'), 'TFLOP/s')"); }
+run() { (cd "$1" && timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 10 --mode "$2" 2>/dev/null | tail -1 | python -c "import sys, json; d = json.loads(sys.stdin.read()); r = d.get('roofline') or {}; h = d.get('host') or {}; print(d['value'], 'clips/s', d['ms_per_step'], 'ms  cpu_ms_per_step', h.get('cpu_ms_per_step'), ' issue_ms_per_step', h.get('issue_ms_per_step'), ' GEMM family', r.get('achieved'), 'TFLOP/s')"); }
 line() { out=$(run "$2" "$3") || { echo "$1 $3: bench run failed, stopping"; exit 1; }; echo "$1 $3: $out"; }
 pairs() { for r in $(seq "$2"); do line old "$old" "$1"; line new . "$1"; done; }
 old=$1; shift

@@ -4,8 +4,9 @@ import collections, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
-from transformer4sed_amd import pmam_engine, ops, synth
+from transformer4sed_amd import ops, synth
 from transformer4sed_amd.engine import context, grads
+from transformer4sed_amd.pmam_engine import grads as pmam_grads
 
 mode = sys.argv[1] if len(sys.argv) > 1 else "pmam"
 dev = torch.device("cuda:0")
@@ -21,7 +22,7 @@ def wrap(mod, name, tag, shape_of):
     setattr(mod, name, f)
 
 
-for mod in (grads, context, pmam_engine):      # (the modules that bind the weight-gradient helpers by name)
+for mod in (grads, context, pmam_grads):      # (the modules that bind the weight-gradient helpers by name)
     if hasattr(mod, "gemm_dw_tn"):
         wrap(mod, "gemm_dw_tn", "TN", lambda dY, X, dW, tokens=None, **k: (tokens or dY.shape[0], dY.shape[1], k.get("k_in") or X.shape[1], str(X.dtype)[6:]))
     wrap(mod, "gemm_dw", "NT split-K", lambda a, b, c, *r, **k: (a.shape[1], a.shape[0], b.shape[0]))

@@ -118,7 +118,7 @@ def branch_level(nets):
         def fwd_bwd(eng=eng, W=W, views=views):
             with torch.no_grad():
                 _, cctx = eng._cnn_fwd(W, mel, train=True, save=True)
-                slots, scatter = eng._grad_slots(B, mel.device, views.get, False, True)
+                slots, scatter = eng._grad_slots(B, mel.device, views.get, False, True, T=mel.shape[2])
                 eng._cnn_bwd(W, cctx, dfeat, B, views.get, slots)
                 eng._join_dw()
                 call("sed_scatter_add_f32", *scatter["cnn"])

@@ -265,7 +265,7 @@ class Context:
     def _decoder_bwd(self, W, dctx, g, G, trainable):
         """Backward of `_decoder_fwd` given g = d(output) [B, T, width]; -> d(input).  Parameter gradients go to the views `G` names
         (the attention's: where `_relattn_sink` says); none is computed when `trainable` is false.  (The PMAM form of the sink needs
-        `dctx["slots"]`: the views of `_grad_slots` made with `dec_train` = `trainable`, as `PmamEngine._context_bwd` leaves them.)"""
+        `dctx["slots"]`: the views of `_grad_slots` made with `dec_train` = `trainable`, as `PmamEngine._context_bwd` (pmam_engine/stages.py) leaves them.)"""
         m = self.m
         B, T, Dm = g.shape
         M = B * T

@@ -2,7 +2,7 @@
 LoRA linears, a 10-layer CNN branch, attention frequency pooling and a 384-wide Transformer-XL context network.  Constructor
 kwargs (`passt_sed_param`, `cnn_param`), forward signature / return values, parameter and buffer names (state_dict interchange,
 including the BatchNorm running statistics and the eval-mode LoRA weight folding) follow the reference; forward runs on the HIP
-kernels of pmam_engine.py.  The nn.Modules are parameter containers only."""
+kernels of the pmam_engine package.  The nn.Modules are parameter containers only."""
 import re
 
 import torch
