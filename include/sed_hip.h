@@ -726,6 +726,16 @@ int sed_longform_stitch(const float* strong, const float* weak, float* out, int 
  * the device, max_size the caller's bound on them (1 .. 1024; a class whose window exceeds it comes out as NaN); modes 1 / 2 need
  * max_size <= T. */
 int sed_longform_filter(const float* in, float* out, const int* sizes, int64_t T, int C, int mode, int max_size, hipStream_t stream);
+/* A bank of the filters of sed_median_filter_k for the post-processing search (csrc/filter_bank.hip): in [B, T, C] ->
+ * out [W, B, T, C], where out[w] holds bit for bit what sed_median_filter_k(in, ., sizes + w C, scale, B, T, C, mode, max_size) writes --
+ * modes 0 / 1 / 2, scale [B, C] or NULL -- for every argument set that kernel accepts (T <= 12288; the order-statistics form for modes 0 / 1
+ * with max_size >= 24, T >= 256 and T + max_size + 1 <= 2048, the rank search otherwise).  sizes [W, C] on the device, one window row per
+ * candidate, free per class; max_size >= 1 is the caller's bound on them and is required here (it sizes the staged column).  One
+ * workgroup per (clip, class) stages the padded column and ranks it once for all W rows.  1 <= W <= 64, B, T, C >= 1; the rank-search form
+ * needs T + max_size - 1 <= 16384 entries of LDS; otherwise SED_ERR_ARG, and nothing is written.  A (row, class) whose window is below 1,
+ * above max_size or (modes 1 / 2) above T comes out as NaN, the other planes intact.  Deterministic: no atomics, every element written once. */
+int sed_median_filter_bank(const float* in, float* out, const int* sizes, const float* scale, int B, int T, int C, int W, int mode,
+                           int max_size, hipStream_t stream);
 /* Events of post [T, C]: frame t of class c is active iff post[t, c] > th[c] (strict), every maximal run is one event.  The timeline is cut
  * into segments of `seg` frames (nseg = ceil(T / seg) <= 65535).
  * sed_longform_event_count: seg_counts [C nseg] (run starts per class and segment, class-major), seg_offs [C nseg + 1] their exclusive

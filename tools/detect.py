@@ -7,7 +7,11 @@ CONFIG.yaml is the recipe's YAML (with its `include:` of a base file, as the rec
 `.init_kwargs` with its `val_kwargs`, the clock under `feature` (sr, hopsize, win_length, audio_max_len, net_subsample), and
 `training.median_window` / `filter_type` / `weak_mask`.  CK.pt is a state dict, or a dict holding one under "state_dict".  Writes
 OUT/scores_raw/<file>.tsv and OUT/scores_post/<file>.tsv (the sed_scores_eval layout `write_sed_scores` writes) and OUT/events.tsv
-(event_label, onset, offset, filename).  Files at another sample rate than the model's are resampled on the device."""
+(event_label, onset, offset, filename).  Files at another sample rate than the model's are resampled on the device.
+
+`--postprocess CHOICE.json` takes the per-class windows (in frames), the filter type and -- where the choice holds them -- the per-class
+thresholds that `tools/tune_postprocess.py` searched on a validation set (transformer4sed_amd.PostprocChoice), in place of the YAML's
+`median_window` / `filter_type` and of `--threshold`."""
 import argparse
 import os
 import sys
@@ -41,6 +45,7 @@ def main(argv=None):
     ap.add_argument("--out", required=True)
     ap.add_argument("--labels", default=None, help="comma-separated class names in the model's order (default: the ten DESED classes)")
     ap.add_argument("--threshold", default="0.5", help="one value, or a comma-separated list with one per class")
+    ap.add_argument("--postprocess", default=None, help="a PostprocChoice JSON (tools/tune_postprocess.py): windows, filter type, thresholds")
     ap.add_argument("--hop-frames", type=int, default=500)
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--gpu", type=int, default=0)
@@ -56,9 +61,17 @@ def main(argv=None):
     enc = Encoder(labels, audio_len=f["audio_max_len"], frame_len=f["win_length"], frame_hop=f["hopsize"], net_pooling=f["net_subsample"],
                   sr=f["sr"])
     device = torch.device("cuda", a.gpu)
-    det = LongFormDetector(load_model(cfg, a.checkpoint, device), enc, cfg, hop_frames=a.hop_frames, batch_size=a.batch_size)
     th = [float(v) for v in a.threshold.split(",")]
     th = th[0] if len(th) == 1 else th
+    override = {}
+    if a.postprocess:
+        from transformer4sed_amd import PostprocChoice
+        choice = PostprocChoice.load(a.postprocess)
+        if list(choice.labels) != list(labels):
+            raise SystemExit(f"{a.postprocess} was searched for the classes {choice.labels}, the model's are {labels}")
+        override = dict(median_filter=choice.windows_frames, filter_type=choice.filter_type)
+        th = choice.thresholds if choice.thresholds is not None else th
+    det = LongFormDetector(load_model(cfg, a.checkpoint, device), enc, cfg, hop_frames=a.hop_frames, batch_size=a.batch_size, **override)
     raw, post, events = {}, {}, []
     for path in a.files:
         wav = det.load(path)

@@ -15,12 +15,16 @@ _TOKENIZER = ("GaussianMixtureTokenizer", "KMeansTokenizer", "FeatureExtractor",
 
 
 _EVALUATION = ("IntersectionPSDS", "compute_psds_from_scores", "EventSegmentF1", "log_sedeval_metrics")
+_SEARCH = ("PostprocSearch", "PostprocChoice")
 
 
 def __getattr__(name):      # the PMAM tokenizer (tokenizer.py), the PSDS and the F1 (evaluation/), resolved on first use: they pull in the op layer
     if name in _TOKENIZER:
         from . import tokenizer
         return getattr(tokenizer, name)
+    if name in _SEARCH:
+        from . import postproc_search
+        return getattr(postproc_search, name)
     if name in _EVALUATION:
         from . import evaluation
         return getattr(evaluation, name)

@@ -225,10 +225,11 @@ class IntersectionPSDS(ClipAccumulator):
             lo += n
         return self._points
 
-    def _class_rocs(self):
-        """Per class the staircase (eFPR ascending, running-maximum TPR), float64, with the empty point first."""
+    def _class_rocs(self, points=None):
+        """Per class the staircase (eFPR ascending, running-maximum TPR), float64, with the empty point first; `points`: operating
+        points in `counts()`'s form instead of this accumulator's own."""
         rocs = []
-        for c, p in enumerate(self.counts()):
+        for c, p in enumerate(self.counts() if points is None else points):
             tpr = np.concatenate(([0.0], p["tp"].astype(np.float64) / float(self.n_ref[c])))
             efpr = np.concatenate(([0.0], (p["fp"].astype(np.float64) / (self.data_us / 1e6)
                                            + self.alpha_ct * (p["ct"].astype(np.float64) * self.ct_unit)) * self.unit))
@@ -252,7 +253,13 @@ class IntersectionPSDS(ClipAccumulator):
         return grid, eff
 
     def compute(self):
-        rocs = self._class_rocs()
+        return self.compute_points(None)
+
+    def compute_points(self, points):
+        """`compute()` on operating points given per class in `counts()`'s form (None: this accumulator's own) -- class c's points may
+        come from another accumulator of the same ground truth and arguments that was fed other scores (a class's points depend on that
+        class's scores alone: `PostprocSearch` composes a per-class choice this way instead of running the sweep again)."""
+        rocs = self._class_rocs(points)
         grid, eff = self._psd_roc(rocs)
         single = {c: self._area(e, y, self.max_efpr) for c, (e, y) in zip(self.event_classes, rocs)}
         return self._area(grid, eff, self.max_efpr), single

@@ -38,3 +38,41 @@ def median_filter_scipy(scores, filter_size, weak_scale=None):
 
 def max_filter_scipy(scores, filter_size, weak_scale=None):
     return _run(scores, filter_size, 2, weak_scale)
+
+
+FILTER_BANK_MAX_ROWS = 64      # csrc/filter_bank.hip: window rows of one launch
+
+
+def check_bank_sizes(sizes, T, C, mode):
+    """The window rows of a bank as [W][C] ints, after the bounds the kernel answers with NaN planes: ValueError first."""
+    if mode not in (0, 1, 2):
+        raise ValueError("mode must be 0 (torch median), 1 (scipy median) or 2 (scipy max)")
+    rows = [[int(s) for s in row] for row in sizes]
+    if not 1 <= len(rows) <= FILTER_BANK_MAX_ROWS:
+        raise ValueError(f"filter_bank takes 1 .. {FILTER_BANK_MAX_ROWS} window rows, got {len(rows)}")
+    for row in rows:
+        if len(row) != C:
+            raise ValueError("every row of sizes must hold one window per class")
+        if min(row) < 1:
+            raise ValueError("window sizes must be at least 1 frame")
+        if mode != 0 and max(row) > T:
+            raise ValueError("scipy-semantics filter: window longer than the sequence is outside the reproduced domain")
+    return rows
+
+
+def filter_bank(x, sizes, mode, scale=None):
+    """x [B, T, C], sizes [W][C] -> [W, B, T, C]: out[w] is bit for bit what `sed_median_filter_k` writes for the row sizes[w] under the
+    bank's bound (the largest window of all rows) -- the values of `_run(x, sizes[w], mode, scale)` -- all W rows from one launch that
+    stages and ranks every (clip, class) column once (csrc/filter_bank.hip)."""
+    if x.dim() != 3:
+        raise ValueError("input_tensor must have shape (Batch, Length, Classes)")
+    B, T, C = x.shape
+    rows = check_bank_sizes(sizes, T, C, mode)
+    x = x.contiguous().float()
+    out = torch.empty((len(rows), B, T, C), dtype=torch.float32, device=x.device)
+    if B == 0 or T == 0:
+        return out
+    sz = h2d(rows, torch.int32, x.device)
+    sc = None if scale is None else scale.contiguous().float()
+    call("sed_median_filter_bank", x, out, sz, sc, B, T, C, len(rows), mode, max(max(r) for r in rows))
+    return out
