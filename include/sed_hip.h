@@ -736,6 +736,17 @@ int sed_longform_filter(const float* in, float* out, const int* sizes, int64_t T
  * above max_size or (modes 1 / 2) above T comes out as NaN, the other planes intact.  Deterministic: no atomics, every element written once. */
 int sed_median_filter_bank(const float* in, float* out, const int* sizes, const float* scale, int B, int T, int C, int W, int mode,
                            int max_size, hipStream_t stream);
+/* Change-detection sound event bounding boxes for a bank of K parameter rows (csrc/sebb.hip; DESIGN.md section 7f, exact in integers): in
+ * [B, T, C] fp32 in [0, 1] (x scale [B, C] or NULL: one fp32 multiply), params [K, C, 3] int32 on the device = (L, tau_q, rho_q) per row and
+ * class: half length of the step filter in frames (>= 1; L >= T is L = T), rint(tau 2^24) in 0 .. 2^24, rint(rho 256) in 256 .. 4096.
+ * -> out [K, B, T, C] (a box's confidence on its frames, 0 elsewhere), boxes [K, B, C, cap, 2] int32 (onset frame, offset frame; onsets
+ * ascending), conf [K, B, C, cap] fp32, counts [K, B, C] int32 (the true number of boxes, also where it exceeds cap), status [2] int32:
+ * status[0] = 1 if some row had more than cap boxes (its first cap are written, nothing past them), status[1] = 1 if a score was NaN or
+ * outside [0, 1] (clamped).  Box slots from min(count, cap) on are left untouched.  One workgroup per (clip, class); steps shared by the
+ * rows with the same L of a class run once.  1 <= T <= 1024, 1 <= K <= 64, 1 <= cap <= 1024 (cap >= (T + 1) / 2 never overflows), B, C >= 1;
+ * otherwise SED_ERR_ARG, and nothing is written.  Deterministic: no atomics, every element written once by a plain store. */
+int sed_sebb_bank(const float* in, const float* scale, const int* params, float* out, int* boxes, float* conf, int* counts, int* status,
+                  int B, int T, int C, int K, int cap, hipStream_t stream);
 /* Events of post [T, C]: frame t of class c is active iff post[t, c] > th[c] (strict), every maximal run is one event.  The timeline is cut
  * into segments of `seg` frames (nseg = ceil(T / seg) <= 65535).
  * sed_longform_event_count: seg_counts [C nseg] (run starts per class and segment, class-major), seg_offs [C nseg + 1] their exclusive

@@ -11,7 +11,9 @@ OUT/scores_raw/<file>.tsv and OUT/scores_post/<file>.tsv (the sed_scores_eval la
 
 `--postprocess CHOICE.json` takes the per-class windows (in frames), the filter type and -- where the choice holds them -- the per-class
 thresholds that `tools/tune_postprocess.py` searched on a validation set (transformer4sed_amd.PostprocChoice), in place of the YAML's
-`median_window` / `filter_type` and of `--threshold`."""
+`median_window` / `filter_type` and of `--threshold`.  A `SebbChoice` (`tools/tune_postprocess.py --sebb`) or a saved `SebbPostprocessor`
+is taken as well: the post-processed scores are then the bounding-box scores of the raw timeline and the events the boxes whose
+confidence exceeds the threshold.  That path covers recordings of up to 1024 frames (one clip); a longer one is refused."""
 import argparse
 import os
 import sys
@@ -45,7 +47,7 @@ def main(argv=None):
     ap.add_argument("--out", required=True)
     ap.add_argument("--labels", default=None, help="comma-separated class names in the model's order (default: the ten DESED classes)")
     ap.add_argument("--threshold", default="0.5", help="one value, or a comma-separated list with one per class")
-    ap.add_argument("--postprocess", default=None, help="a PostprocChoice JSON (tools/tune_postprocess.py): windows, filter type, thresholds")
+    ap.add_argument("--postprocess", default=None, help="a PostprocChoice JSON (tools/tune_postprocess.py): windows, filter type, thresholds; or a SebbChoice / SebbPostprocessor JSON")
     ap.add_argument("--hop-frames", type=int, default=500)
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--gpu", type=int, default=0)
@@ -63,8 +65,17 @@ def main(argv=None):
     device = torch.device("cuda", a.gpu)
     th = [float(v) for v in a.threshold.split(",")]
     th = th[0] if len(th) == 1 else th
-    override = {}
-    if a.postprocess:
+    override, sebb = {}, None
+    from transformer4sed_amd.sebb import SEBB_MAX_FRAMES, SebbPostprocessor, is_sebb_file
+    if a.postprocess and is_sebb_file(a.postprocess):
+        import json
+        try:
+            sebb = SebbPostprocessor.load(a.postprocess, enc)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        with open(a.postprocess) as saved:
+            th = json.load(saved).get("thresholds") or th          # (a SebbChoice of an F1 objective holds per-class thresholds)
+    elif a.postprocess:
         from transformer4sed_amd import PostprocChoice
         choice = PostprocChoice.load(a.postprocess)
         if list(choice.labels) != list(labels):
@@ -77,6 +88,10 @@ def main(argv=None):
         wav = det.load(path)
         audio_id = os.path.splitext(os.path.basename(path))[0]
         out = det.posteriors(wav)                    # one pass of the model for the tables and the events
+        if sebb is not None:
+            if out["raw"].shape[0] > SEBB_MAX_FRAMES:
+                raise SystemExit(f"{path}: {out['raw'].shape[0]} frames; bounding boxes cover up to {SEBB_MAX_FRAMES} (long-form is out of scope)")
+            out["post"] = sebb.scores_btc(out["raw"][None])[0]
         r, p = det.tables(out, audio_id)
         raw.update(r)
         post.update(p)

@@ -13,7 +13,11 @@ holding the EMA weights under "ema_state_dict".  Every batch is read with `data.
 
 Prints the table (one row per objective, filter type, candidate[, threshold] and class), and writes OUT/search_table.tsv, one
 OUT/choice_<objective>.json per searched objective (what `tools/detect.py --postprocess` takes; `--objective` names the one also written
-as OUT/choice.json) and OUT/postprocess.yaml, the fragment for the recipe's `training:` section."""
+as OUT/choice.json) and OUT/postprocess.yaml, the fragment for the recipe's `training:` section.
+
+`--sebb` searches sound event bounding boxes instead (transformer4sed_amd.SebbSearch): the candidates are the grid `--step-filter-lengths`
+(seconds) x `--merge-thresholds-abs` x `--merge-thresholds-rel`, `--windows` / `--filter-types` play no part, and the choices are
+`SebbChoice` files, which `tools/detect.py --postprocess` takes as well."""
 import argparse
 import os
 import sys
@@ -38,6 +42,10 @@ def main(argv=None):
     ap.add_argument("--objectives", default="psds1,psds2", help="of psds1, psds2, event_f1, segment_f1")
     ap.add_argument("--thresholds", default="0.5", help="comma-separated thresholds of the F1 objectives")
     ap.add_argument("--objective", default=None, help="the objective whose choice becomes choice.json / postprocess.yaml (default: the first)")
+    ap.add_argument("--sebb", action="store_true", help="search sound event bounding boxes (a grid of SEBB parameters) instead of filter windows")
+    ap.add_argument("--step-filter-lengths", default=None, help="with --sebb: comma-separated seconds (default: 0.32,0.48,0.64)")
+    ap.add_argument("--merge-thresholds-abs", default=None, help="with --sebb (default: 0.15,0.2,0.3)")
+    ap.add_argument("--merge-thresholds-rel", default=None, help="with --sebb (default: 1.5,2,3)")
     ap.add_argument("--sr-in", type=int, default=16000)
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--gpu", type=int, default=0)
@@ -45,7 +53,7 @@ def main(argv=None):
     import pandas as pd
     import torch
     import detect
-    from transformer4sed_amd import PostprocSearch
+    from transformer4sed_amd import PostprocSearch, SebbSearch
     from transformer4sed_amd.compat.src.utils import load_yaml_with_relative_ref
     from transformer4sed_amd.data import WavBatchStream
     from transformer4sed_amd.evaluation import Encoder
@@ -70,10 +78,16 @@ def main(argv=None):
     kw = cfg[net.get_model_name()]["val_kwargs"]
     tr = cfg.get("training", {})
     objectives = a.objectives.split(",")
-    search = PostprocSearch(enc, a.tsv, a.durations, objectives=objectives, filter_types=a.filter_types.split(","),
-                            thresholds=[float(v) for v in a.thresholds.split(",")], weak_mask=tr.get("weak_mask", False),
-                            config_windows=tr.get("median_window"),
-                            **({"windows": [float(v) if "." in v else int(v) for v in a.windows.split(",")]} if a.windows else {}))
+    thresholds = [float(v) for v in a.thresholds.split(",")]
+    if a.sebb:
+        grid = {k: [float(v) for v in given.split(",")] for k, given in (("step_filter_lengths", a.step_filter_lengths),
+                                                                         ("merge_thresholds_abs", a.merge_thresholds_abs),
+                                                                         ("merge_thresholds_rel", a.merge_thresholds_rel)) if given}
+        search = SebbSearch(enc, a.tsv, a.durations, objectives=objectives, thresholds=thresholds, weak_mask=tr.get("weak_mask", False), **grid)
+    else:
+        search = PostprocSearch(enc, a.tsv, a.durations, objectives=objectives, filter_types=a.filter_types.split(","),
+                                thresholds=thresholds, weak_mask=tr.get("weak_mask", False), config_windows=tr.get("median_window"),
+                                **({"windows": [float(v) if "." in v else int(v) for v in a.windows.split(",")]} if a.windows else {}))
     names = list(pd.read_csv(a.durations, sep="\t")["filename"])
     paths = [os.path.join(a.wav_dir, n) for n in names]
     batches = [list(range(s, min(s + a.batch_size, len(paths)))) for s in range(0, len(paths), a.batch_size)]
@@ -91,9 +105,12 @@ def main(argv=None):
     for name in objectives:
         best = search.best(name)
         best.save(os.path.join(a.out, f"choice_{name}.json"))
-        gain = "" if best.config_overall is None else f" (the YAML's own list: {best.config_overall:.4f})"
-        print(f"{name}: {best.filter_type}, median_window {best.windows_units} = {best.windows_frames} frames"
-              + (f", thresholds {best.thresholds}" if best.thresholds is not None else "") + f" -> {best.overall:.4f}{gain}")
+        if a.sebb:
+            what, gain = f"sebb, {best.to_config()['sebb']} = half lengths {best.half_lengths} frames", ""
+        else:
+            what = f"{best.filter_type}, median_window {best.windows_units} = {best.windows_frames} frames"
+            gain = "" if best.config_overall is None else f" (the YAML's own list: {best.config_overall:.4f})"
+        print(f"{name}: {what}" + (f", thresholds {best.thresholds}" if best.thresholds is not None else "") + f" -> {best.overall:.4f}{gain}")
         if name == main_objective:
             best.save(os.path.join(a.out, "choice.json"))
             with open(os.path.join(a.out, "postprocess.yaml"), "w") as out:

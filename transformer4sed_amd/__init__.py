@@ -16,6 +16,7 @@ _TOKENIZER = ("GaussianMixtureTokenizer", "KMeansTokenizer", "FeatureExtractor",
 
 _EVALUATION = ("IntersectionPSDS", "compute_psds_from_scores", "EventSegmentF1", "log_sedeval_metrics")
 _SEARCH = ("PostprocSearch", "PostprocChoice")
+_SEBB = ("sebb_bank", "SebbPostprocessor", "SebbSearch", "SebbChoice")
 
 
 def __getattr__(name):      # the PMAM tokenizer (tokenizer.py), the PSDS and the F1 (evaluation/), resolved on first use: they pull in the op layer
@@ -25,6 +26,9 @@ def __getattr__(name):      # the PMAM tokenizer (tokenizer.py), the PSDS and th
     if name in _SEARCH:
         from . import postproc_search
         return getattr(postproc_search, name)
+    if name in _SEBB:
+        from . import sebb
+        return getattr(sebb, name)
     if name in _EVALUATION:
         from . import evaluation
         return getattr(evaluation, name)

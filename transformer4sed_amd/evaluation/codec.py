@@ -108,13 +108,16 @@ def check_filter_type(filter_type):
     return filter_type
 
 
-def _scores_device(strong_preds, n, filter, filter_type, weak_preds, need_weak_mask):
-    """Device half of `batched_decode_preds`: (raw, post) [n, frames, n_class] fp32 device tensors (post None without a filter)."""
+def _scores_device(strong_preds, n, filter, filter_type, weak_preds, need_weak_mask, sebb=None):
+    """Device half of `batched_decode_preds`: (raw, post) [n, frames, n_class] fp32 device tensors (post None without a filter).  `sebb`:
+    a `sebb.SebbPostprocessor` whose frame scores take the filter's place."""
     x = strong_preds[:n].detach().transpose(1, 2).contiguous().float()          # [bs, frames, n_class]
     scale = weak_preds[:n].detach().float() if (need_weak_mask and weak_preds is not None) else None
     raw = x if scale is None else x * scale.unsqueeze(1)
     post = None
-    if filter:
+    if sebb is not None:
+        post = sebb.scores_btc(x, scale, check=False)         # (no read from the device here: the kernel clamps what the check refuses)
+    elif filter:
         run = dev_filter.median_filter_scipy if filter_type == "median" else dev_filter.max_filter_scipy
         post = run(x, list(filter), weak_scale=scale)
     return raw, post
@@ -140,27 +143,30 @@ def _scores_tables(raw_h, post_h, filenames, encoder, pad_indx, n_frames):
 
 
 def batched_decode_preds(strong_preds, filenames, encoder, filter=7, filter_type="median", pad_indx=None, weak_preds=None,
-                         need_weak_mask=None):
+                         need_weak_mask=None, sebb=None):
     """src/codec/decoder.py:38-103.  strong_preds [bs, n_class, frames] (device tensor), weak_preds [bs, n_class].
-    Returns (scores_raw, scores_postprocessed): dicts audio_id -> score DataFrame.  `filter`: per-class window list."""
+    Returns (scores_raw, scores_postprocessed): dicts audio_id -> score DataFrame.  `filter`: per-class window list.  `sebb` (not in the
+    reference): a `SebbPostprocessor` that post-processes in place of `filter` / `filter_type`."""
     check_filter_type(filter_type)
     n = min(strong_preds.shape[0], len(filenames))      # the reference loops over strong_preds and indexes filenames[j]
     if strong_preds.shape[0] > len(filenames):
         raise IndexError("list index out of range")     # same failure as the reference's filenames[j]
     if n == 0:
         return {}, {}
-    raw, post = _scores_device(strong_preds, n, filter, filter_type, weak_preds, need_weak_mask)
+    raw, post = _scores_device(strong_preds, n, filter, filter_type, weak_preds, need_weak_mask, sebb)
     return _scores_tables(raw.cpu().numpy(), post.cpu().numpy() if post is not None else None, filenames, encoder, pad_indx,
                           strong_preds.shape[-1])
 
 
-def _events_device(outputs, weak_preds, thresholds, median_filter):
-    """Device half of `decode_pred_batch_fast`: one bool tensor [batch, frames, n_class] per threshold."""
+def _events_device(outputs, weak_preds, thresholds, median_filter, sebb=None):
+    """Device half of `decode_pred_batch_fast`: one bool tensor [batch, frames, n_class] per threshold.  With `sebb` the frames of the
+    boxes whose confidence exceeds the threshold, in place of the median-filtered frames above it."""
     x = outputs.detach().transpose(1, 2).contiguous().float()
     out = []
     for c_th in thresholds:
         keep = (weak_preds.detach() >= c_th).float()              # output[b, :, c] = 0 where weak_preds[b, c] < c_th
-        out.append(dev_filter._run(x, list(median_filter), 0, keep) > c_th)
+        post = dev_filter._run(x, list(median_filter), 0, keep) if sebb is None else sebb.scores_btc(x, keep, check=False)
+        out.append(post > c_th)
     return out
 
 

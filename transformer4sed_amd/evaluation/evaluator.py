@@ -46,7 +46,7 @@ class _HostStage:
             self.event = None
 
 
-def _enqueue_scores(stage, strong, weak, paths, median_filter, filter_type, weak_mask):
+def _enqueue_scores(stage, strong, weak, paths, median_filter, filter_type, weak_mask, sebb=None):
     """Device half of one model's score tables: filters, raw and post-processed scores on their way into `stage`'s pinned buffers.
     -> (job for `_finish_scores`, the scores the metrics take, still on the device; None for an empty batch).  `stage.mark()` is the caller's."""
     if strong.shape[0] > len(paths):
@@ -54,7 +54,7 @@ def _enqueue_scores(stage, strong, weak, paths, median_filter, filter_type, weak
     job = {"paths": list(paths), "n": strong.shape[0], "frames": strong.shape[-1], "stage": stage, "raw": None, "post": None}
     if job["n"] == 0:
         return job, None
-    raw, post = _scores_device(strong, job["n"], median_filter, filter_type, weak, weak_mask)
+    raw, post = _scores_device(strong, job["n"], median_filter, filter_type, weak, weak_mask, sebb)
     job["raw"] = stage.put("raw", raw)
     job["post"] = stage.put("post", post) if post is not None else None
     return job, post if post is not None else raw
@@ -97,13 +97,16 @@ class Evaluator(_GroundTruthMetrics):
     right behind each forward with `.cpu()` -- left the GPU idle for 14 of a 212 ms validation step, tools/ablate/step_gaps.sh.)
 
     With `ground_truth=` / `audio_durations=` the post-processed scores and the binarised frames also feed, still on the device, the
-    PSDS accumulators (`psds()`) and one `EventSegmentF1` per model (`f1()`)."""
+    PSDS accumulators (`psds()`) and one `EventSegmentF1` per model (`f1()`).
+
+    `sebb=`: a `sebb.SebbPostprocessor`; its bounding-box scores take the place of both filters -- of the scipy filter behind the
+    post-processed tables and the PSDS, and of the torch median behind the half-point events and the F1."""
 
     PSDS_ARGS = {"psds1": dict(dtc_threshold=0.7, gtc_threshold=0.7, cttc_threshold=None, alpha_ct=0, alpha_st=1),      # train.py:229-253
                  "psds2": dict(dtc_threshold=0.1, gtc_threshold=0.1, cttc_threshold=0.3, alpha_ct=0.5, alpha_st=1)}
 
-    def __init__(self, net, ema_net, encoder, config, ground_truth=None, audio_durations=None):
-        self.net, self.ema_net, self.encoder, self.config = net, ema_net, encoder, config
+    def __init__(self, net, ema_net, encoder, config, ground_truth=None, audio_durations=None, sebb=None):
+        self.net, self.ema_net, self.encoder, self.config, self.sebb = net, ema_net, encoder, config, sebb
         self._pair_tables(ground_truth, audio_durations)
         self._psds = None           # who -> {"psds1": IntersectionPSDS, "psds2": ...}, made at the first batch (it brings the frame count)
         self._f1 = None             # who -> EventSegmentF1, likewise
@@ -120,11 +123,11 @@ class Evaluator(_GroundTruthMetrics):
     # ---- device half of one model's decode: filters, thresholds, device-to-host copies into pinned buffers, one event
     def _enqueue(self, who, strong, weak, paths):
         st = self._stage[who]
-        job, scores = _enqueue_scores(st, strong, weak, paths, self.median_filter, self.filter_type, self.weak_mask)
+        job, scores = _enqueue_scores(st, strong, weak, paths, self.median_filter, self.filter_type, self.weak_mask, self.sebb)
         job["who"], n = who, job["n"]
         if self._psds_tables is not None and n > 0:
             self._psds_update(who, scores, paths[:n])
-        binm = _events_device(strong, weak, [0.5], self.median_filter)[0]
+        binm = _events_device(strong, weak, [0.5], self.median_filter, self.sebb)[0]
         if self._psds_tables is not None and n > 0:
             self._f1_update(who, binm, paths[:n])
         job["bin"] = st.put("bin", binm)
