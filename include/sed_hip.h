@@ -84,6 +84,34 @@ int sed_ap_grow(const float* old_scores, const uint8_t* old_labels, int C, int n
                 int new_cap, hipStream_t stream);
 int sed_ap_compute(const float* scores, const uint8_t* labels, int C, int N, int cap, int chunk, uint32_t* all_sorted, uint32_t* pos_sorted,
                    int* pos_cnt, unsigned long long* partial, double* ap, int* npos, hipStream_t stream);
+/* ROC area and partial ROC area from the same storage (csrc/metrics.hip; DESIGN.md section 7g holds the definition): the AUC / d' that
+ * AudioSet systems report beside the mAP, and the per-class integers of the segment-based mpAUC that src/utils/validate_submissions.py:111
+ * asks for on MAESTRO.  out: int64 [C][SED_ROC_OUT] = P, Nn, auc2, area2, fp_a, tp_a, fp_b, tp_b over items 0 .. N-1, where point a is
+ * the last ROC point with fp <= floor(max_fpr Nn) (max_fpr in (0, 1]) and b the next one; the caller finishes in float64.  chunk
+ * (1 .. SED_ROC_MAX_CHUNK) and all_sorted / pos_sorted / pos_cnt as for sed_ap_compute; scratch: uint64 [C (2 ceil(N/chunk) + 1)].  With
+ * N <= chunk only scores, labels and out are touched.  The result does not depend on item order or chunk. */
+#define SED_ROC_OUT 8
+#define SED_ROC_MAX_CHUNK 20000
+int sed_roc_compute(const float* scores, const uint8_t* labels, int C, int N, int cap, int chunk, double max_fpr, uint32_t* all_sorted,
+                    uint32_t* pos_sorted, int* pos_cnt, unsigned long long* scratch, long long* out, hipStream_t stream);
+/* Segment scores from frame scores on the device (csrc/segment_pool.hip): get_segment_scores and
+ * get_segment_scores_and_overlap_add of src/codec/decoder.py:138-230.
+ * sed_segment_pool: scores [n,T,C] f32, ts_us [T+1] frame boundaries in microseconds (not decreasing), per clip its length clip_len_us
+ * and the row row_off of its first segment in pooled [cap_rows][C] f32; clip i fills ceil(clip_len_us[i] / seg_us) <= max_seg rows with
+ * the duration-weighted means of its frames.
+ * sed_segment_gather: file segment s of S averages the pooled rows rows[ptr[s] .. ptr[s+1]) (CSR, at most max_rows each, nnz in all,
+ * each below n_rows) in the order given; out [C][ld] f32 class-major (ld >= S), 0 for a segment without a row.
+ * status: int [SED_SEG_STATUS_WORDS], sticky, zeroed once by the caller; a word is set to 1 for: a segment without weight, a NaN
+ * score, a row outside the storage, a row list longer than max_rows. */
+#define SED_SEG_STATUS_WORDS 4
+#define SED_SEG_ZERO_WEIGHT 0
+#define SED_SEG_NAN 1
+#define SED_SEG_BAD_ROW 2
+#define SED_SEG_LONG_LIST 3
+int sed_segment_pool(const float* scores, const int64_t* ts_us, const int64_t* clip_len_us, const int* row_off, int64_t seg_us, int n,
+                     int T, int C, int max_seg, int cap_rows, float* pooled, int* status, hipStream_t stream);
+int sed_segment_gather(const float* pooled, const int* ptr, const int* rows, int S, int C, int n_rows, int nnz, int max_rows, int ld,
+                       float* out, int* status, hipStream_t stream);
 /* Intersection-based PSDS (Bilen et al. 2020, over all score values as in Ebbers et al. 2022): what src/evaluation_measures.py:299-341
  * `compute_psds_from_scores` gets from sed_scores_eval, and the objective metric of recipes/desed/finetune/train.py:229-253, 370-398
  * (csrc/psds.hip; DESIGN.md section 7b holds the definition).

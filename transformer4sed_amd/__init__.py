@@ -14,7 +14,7 @@ from .longform import LongFormDetector, chunk_plan, decode_events, median_filter
 _TOKENIZER = ("GaussianMixtureTokenizer", "KMeansTokenizer", "FeatureExtractor", "PseudoLabelGenerator", "save_prob")
 
 
-_EVALUATION = ("IntersectionPSDS", "compute_psds_from_scores", "EventSegmentF1", "log_sedeval_metrics")
+_EVALUATION = ("IntersectionPSDS", "compute_psds_from_scores", "EventSegmentF1", "log_sedeval_metrics", "MultilabelAUROC", "SegmentAUROC")
 _SEARCH = ("PostprocSearch", "PostprocChoice")
 _SEBB = ("sebb_bank", "SebbPostprocessor", "SebbSearch", "SebbChoice")
 

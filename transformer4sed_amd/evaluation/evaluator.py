@@ -368,6 +368,13 @@ class AudiosetStrongEvaluator(_GroundTruthMetrics):
     def compute_map(self):
         return self.map.compute()
 
+    def compute_auroc(self, max_fpr=None):
+        """The AUC and d' AudioSet systems report beside the mAP, from the storage `compute_map` sorts:
+        {"auroc": macro AUROC (sklearn's standardised partial area with `max_fpr`), "d_prime": sqrt(2) ndtri(macro AUROC),
+        "per_class": int64 [C][8]}."""
+        from .roc import storage_auroc
+        return storage_auroc(self.map, max_fpr)
+
     def mean_psds_per_type(self, single_psds):
         return mean_psds_per_type(single_psds, self.type_dict)
 

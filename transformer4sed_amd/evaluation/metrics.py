@@ -1,5 +1,5 @@
 """Clip-level validation metrics: weak F1 (torchmetrics MultilabelF1Score as train.py:277-287 uses it) and multilabel average
-precision on HIP kernels (csrc/metrics.hip)."""
+precision on HIP kernels (csrc/metrics.hip), with the class-major score storage that `roc.MultilabelAUROC` shares."""
 import torch
 
 from ..ops import call
@@ -42,33 +42,10 @@ class WeakF1Macro:
         return float(f1.mean())
 
 
-AP_CHUNK = 20000        # clips per LDS sort of sed_ap_compute (its maximum): the validation split (16 891 clips) is one chunk
-
-
-class MultilabelAveragePrecision:
-    """torchmetrics 0.11 `MultilabelAveragePrecision(num_labels, average, thresholds=None)` as the AudioSet-Strong recipes construct it
-    (passt_cnn/train.py:239-314, detect_any_sound/passt/train.py:134-211, open_vocabulary.py:146-227), on HIP kernels (csrc/metrics.hip).
-
-    `update(preds [B, C], target [B, C])` appends the batch to class-major device storage in one stream-ordered call and never waits for the
-    device.  Like torchmetrics, a batch with any score outside [0, 1] is stored as its sigmoid (decided per batch, on the device).  The
-    target may be integer, bool or a {0, 1}-valued float: the passt_cnn loop hands over a float target (train.py:267); whether 0.11 itself
-    accepts one is not checked here.  Scores are kept as fp32.  `compute()` raises on what torchmetrics' argument validation rejects: no
-    update, a target outside {0, 1}, a NaN score.  `compute_on_step` is accepted and ignored (calling the object updates and returns None).
-    `average`: "macro" (mean over classes with a positive), "weighted" (weights = positives per class), None / "none" ([C]); a class without
-    a positive scores NaN and is left out of both averages with torchmetrics' warning.  "micro" is not implemented."""
-
-    def __init__(self, num_labels, average="macro", compute_on_step=None, chunk=AP_CHUNK, **kwargs):
-        if average == "micro":
-            raise NotImplementedError("MultilabelAveragePrecision: average='micro' is not implemented on the HIP path")
-        if average not in ("macro", "weighted", "none", None):
-            raise ValueError(f"Expected argument `average` to be one of ('macro', 'weighted', 'none', None), but got {average}")
-        for k, v in kwargs.items():
-            if k == "thresholds" and v is None or k == "validate_args" or k == "ignore_index" and v is None:
-                continue
-            raise NotImplementedError(f"MultilabelAveragePrecision: unsupported argument {k}={v!r}")
-        self.num_labels, self.average, self.chunk = int(num_labels), average, int(chunk)
-        self.device = None
-        self.reset()
+class ClassMajorScores:
+    """The append / grow / status storage `MultilabelAveragePrecision` and `roc.MultilabelAUROC` share (csrc/metrics.hip): class-major
+    `scores` [C][cap] fp32 and `labels` [C][cap] uint8 on the device of the first batch, `n` items so far, torchmetrics' per-batch
+    sigmoid rule applied on the device by `sed_ap_append`, and the sticky status word `_checked` reads."""
 
     def reset(self):
         self.n = 0
@@ -111,15 +88,48 @@ class MultilabelAveragePrecision:
         call("sed_ap_append", p, t, B, self.num_labels, self.n, self.cap, self._flag, self._status, self.scores, self.labels)
         self.n += B
 
-    def per_class(self):
-        """-> (ap [C] float64, positives [C] int32), device tensors."""
+    def _checked(self):
+        """Raises on what torchmetrics' argument validation rejects; reads the status word (the one wait for the device)."""
         if self.n == 0:
-            raise RuntimeError("MultilabelAveragePrecision.compute() called before any update")
+            raise RuntimeError(f"{type(self).__name__}.compute() called before any update")
         status = int(self._status.item())
         if status & 4:
             raise RuntimeError("Detected the following values in `target`: values outside {0, 1}; expected only 0 and 1")
         if status & 2:
             raise RuntimeError("Detected NaN values in `preds`")
+
+
+AP_CHUNK = 20000        # clips per LDS sort of sed_ap_compute (its maximum): the validation split (16 891 clips) is one chunk
+
+
+class MultilabelAveragePrecision(ClassMajorScores):
+    """torchmetrics 0.11 `MultilabelAveragePrecision(num_labels, average, thresholds=None)` as the AudioSet-Strong recipes construct it
+    (passt_cnn/train.py:239-314, detect_any_sound/passt/train.py:134-211, open_vocabulary.py:146-227), on HIP kernels (csrc/metrics.hip).
+
+    `update(preds [B, C], target [B, C])` appends the batch to class-major device storage in one stream-ordered call and never waits for the
+    device.  Like torchmetrics, a batch with any score outside [0, 1] is stored as its sigmoid (decided per batch, on the device).  The
+    target may be integer, bool or a {0, 1}-valued float: the passt_cnn loop hands over a float target (train.py:267); whether 0.11 itself
+    accepts one is not checked here.  Scores are kept as fp32.  `compute()` raises on what torchmetrics' argument validation rejects: no
+    update, a target outside {0, 1}, a NaN score.  `compute_on_step` is accepted and ignored (calling the object updates and returns None).
+    `average`: "macro" (mean over classes with a positive), "weighted" (weights = positives per class), None / "none" ([C]); a class without
+    a positive scores NaN and is left out of both averages with torchmetrics' warning.  "micro" is not implemented."""
+
+    def __init__(self, num_labels, average="macro", compute_on_step=None, chunk=AP_CHUNK, **kwargs):
+        if average == "micro":
+            raise NotImplementedError("MultilabelAveragePrecision: average='micro' is not implemented on the HIP path")
+        if average not in ("macro", "weighted", "none", None):
+            raise ValueError(f"Expected argument `average` to be one of ('macro', 'weighted', 'none', None), but got {average}")
+        for k, v in kwargs.items():
+            if k == "thresholds" and v is None or k == "validate_args" or k == "ignore_index" and v is None:
+                continue
+            raise NotImplementedError(f"MultilabelAveragePrecision: unsupported argument {k}={v!r}")
+        self.num_labels, self.average, self.chunk = int(num_labels), average, int(chunk)
+        self.device = None
+        self.reset()
+
+    def per_class(self):
+        """-> (ap [C] float64, positives [C] int32), device tensors."""
+        self._checked()
         C, N, ch = self.num_labels, self.n, self.chunk
         nch = (N + ch - 1) // ch
         dev = self.device
