@@ -764,6 +764,16 @@ int sed_longform_filter(const float* in, float* out, const int* sizes, int64_t T
  * above max_size or (modes 1 / 2) above T comes out as NaN, the other planes intact.  Deterministic: no atomics, every element written once. */
 int sed_median_filter_bank(const float* in, float* out, const int* sizes, const float* scale, int B, int T, int C, int W, int mode,
                            int max_size, hipStream_t stream);
+/* Score-level ensembling for a bank of weight rows (csrc/ensemble.hip): members, a device table of M pointers to
+ * x_m [n, T_m, C] f32 contiguous, Tm [M] int32 on the device (1 <= T_m; the caller keeps T_m <= T), w [W, M, C] f32 on the device, already
+ * normalised (sum over m = 1) -> out [W, n, T, C] f32.  Member m is resampled to T frames by the linear half-pixel rule with the source
+ * coordinate in integers (T_m == T: a copy, T_m == 1: a broadcast).  mode 0: y = sum_m w v_m, m ascending, unfused fp32, bit for bit a
+ * float32 host restatement; mode 1: y = sigmoid(sum_m w logit(clamp(v_m, 1e-7f, 1 - 1e-7f))), in float64, rounded to fp32 at the end.
+ * decimals -1: no rounding, 0 .. 9: y = rintf(y 10^d) / 10^d.  1 <= M <= 8, 1 <= W <= 64, W M C <= 32768 (the weights' LDS), n, T, C >= 1;
+ * otherwise SED_ERR_ARG, and nothing is written.  The members are read once for all W rows; grid-stride over at most 1024 workgroups of
+ * 256 threads; deterministic: no atomics, every element written once. */
+int sed_ensemble_bank(const float* const* members, const int* Tm, const float* w, float* out, int M, int W, int n, int T, int C, int mode,
+                      int decimals, hipStream_t stream);
 /* Change-detection sound event bounding boxes for a bank of K parameter rows (csrc/sebb.hip; DESIGN.md section 7f, exact in integers): in
  * [B, T, C] fp32 in [0, 1] (x scale [B, C] or NULL: one fp32 multiply), params [K, C, 3] int32 on the device = (L, tau_q, rho_q) per row and
  * class: half length of the step filter in frames (>= 1; L >= T is L = T), rint(tau 2^24) in 0 .. 2^24, rint(rho 256) in 256 .. 4096.

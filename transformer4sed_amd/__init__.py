@@ -17,6 +17,7 @@ _TOKENIZER = ("GaussianMixtureTokenizer", "KMeansTokenizer", "FeatureExtractor",
 _EVALUATION = ("IntersectionPSDS", "compute_psds_from_scores", "EventSegmentF1", "log_sedeval_metrics", "MultilabelAUROC", "SegmentAUROC")
 _SEARCH = ("PostprocSearch", "PostprocChoice")
 _SEBB = ("sebb_bank", "SebbPostprocessor", "SebbSearch", "SebbChoice")
+_ENSEMBLE = ("EnsembleSearch", "EnsembleChoice")
 
 
 def __getattr__(name):      # the PMAM tokenizer (tokenizer.py), the PSDS and the F1 (evaluation/), resolved on first use: they pull in the op layer
@@ -29,6 +30,9 @@ def __getattr__(name):      # the PMAM tokenizer (tokenizer.py), the PSDS and th
     if name in _SEBB:
         from . import sebb
         return getattr(sebb, name)
+    if name in _ENSEMBLE:
+        from . import ensemble
+        return getattr(ensemble, name)
     if name in _EVALUATION:
         from . import evaluation
         return getattr(evaluation, name)
