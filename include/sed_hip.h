@@ -65,7 +65,7 @@ int sed_median_filter(const float* in, float* out, const int* sizes, const float
 /* the same filters with the caller's bound `max_size` on the window sizes (which live on the device): with it, windows of 24 frames and more
  * (the evaluation path filters with 32 / 128 frames, recipes/desed/finetune/train.py:221-227) take an order-statistics kernel -- global
  * ranks of the padded column once, windows as bitmaps over ranks -- instead of the O(k^2) rank search; same element selected, bit-exact.
- * A window larger than max_size traps. */
+ * In that kernel a window larger than max_size comes out as a NaN plane for its (clip, class).  csrc/median_filter.hip. */
 int sed_median_filter_k(const float* in, float* out, const int* sizes, const float* scale, int B, int T, int C, int mode,
                         int max_size, hipStream_t stream);
 /* Multilabel average precision, torchmetrics 0.11 MultilabelAveragePrecision with thresholds=None (the AudioSet-Strong validation metric,
@@ -754,7 +754,7 @@ int sed_longform_stitch(const float* strong, const float* weak, float* out, int 
  * the device, max_size the caller's bound on them (1 .. 1024; a class whose window exceeds it comes out as NaN); modes 1 / 2 need
  * max_size <= T. */
 int sed_longform_filter(const float* in, float* out, const int* sizes, int64_t T, int C, int mode, int max_size, hipStream_t stream);
-/* A bank of the filters of sed_median_filter_k for the post-processing search (csrc/filter_bank.hip): in [B, T, C] ->
+/* A bank of the filters of sed_median_filter_k for the post-processing search (csrc/median_filter.hip): in [B, T, C] ->
  * out [W, B, T, C], where out[w] holds bit for bit what sed_median_filter_k(in, ., sizes + w C, scale, B, T, C, mode, max_size) writes --
  * modes 0 / 1 / 2, scale [B, C] or NULL -- for every argument set that kernel accepts (T <= 12288; the order-statistics form for modes 0 / 1
  * with max_size >= 24, T >= 256 and T + max_size + 1 <= 2048, the rank search otherwise).  sizes [W, C] on the device, one window row per

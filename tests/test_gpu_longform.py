@@ -151,6 +151,30 @@ def test_long_filter_refusals_and_limits():
         assert np.array_equal(got, LC.filter_ref(xx, [k, 3], mode)), mode
 
 
+@pytest.mark.parametrize("partly", [False, True])
+@pytest.mark.parametrize("mode", [0, 1])
+def test_long_filter_nan_column(mode, partly):
+    """T = 300, windows [24, 33] (both by global ranks): column 0 all NaN comes out all NaN -- the references' own answer, see
+    test_gpu_postproc_search.test_nan_column_is_a_nan_column_in_the_clip_kernel; with every 7th frame NaN its values are unspecified.
+    Either way the launch returns, writes nothing behind the buffer and column 1 holds the bits of the launch on a finite column 0."""
+    T, C, sizes = 300, 2, [24, 33]
+    x = LC.filter_input(T, 10, seed=5)[:, :C].copy()
+    x_bad = x.copy()
+    x_bad[::7 if partly else 1, 0] = np.nan
+    out = []
+    for inp in (x, x_bad):
+        buf = torch.full((T * C + 64,), SENTINEL, dtype=torch.float32, device=DEV)
+        call("sed_longform_filter", torch.from_numpy(inp).to(DEV), buf, h2d(sizes, torch.int32, buf.device), T, C, mode, max(sizes))
+        got = buf.cpu().numpy()
+        assert np.all(got[T * C:] == SENTINEL)
+        out.append(got[:T * C].reshape(T, C))
+    want, got = out
+    assert not np.isnan(want).any()
+    assert np.array_equal(got[:, 1].view(np.int32), want[:, 1].view(np.int32))
+    if not partly:
+        assert np.isnan(got[:, 0]).all()
+
+
 # ------------------------------------------------------------------------------------------------------------------ events
 @pytest.mark.parametrize("T", [1, 2, LF.EVENT_TILE, 3 * LF.EVENT_TILE + 1])
 def test_events_vs_find_contiguous_regions(T):

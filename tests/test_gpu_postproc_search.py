@@ -1,4 +1,4 @@
-"""The post-processing search on the device (csrc/filter_bank.hip, transformer4sed_amd/postproc_search.py): the filter
+"""The post-processing search on the device (csrc/median_filter.hip, transformer4sed_amd/postproc_search.py): the filter
 bank bit for bit against per-row `sed_median_filter_k` launches and against the host filters of tests/search_cases.py, then the search on
 the planted case against the same search run through the host stand-ins, `Evaluator` and per-threshold `EventSegmentF1` runs."""
 import os
@@ -119,6 +119,94 @@ def test_window_out_of_range_is_a_nan_plane(T, mode):
     if mode != 0 and T == 31:                           # 40 > T under a bound that admits it
         got, _ = _launch_bank(x_d, rows, mode, None, 64)
         assert np.isnan(got[bad]).all() and np.array_equal(got[~bad], SC.bank_ref(x, ok_rows, mode)[~bad])
+
+
+def _launch_clip(x_d, sizes, mode, scale_d, max_size):
+    """-> (out [B, T, C], guard [GUARD]) of one raw `sed_median_filter_k` launch into a sentinel-filled buffer."""
+    B, T, C = x_d.shape
+    buf = torch.full((B * T * C + GUARD,), SENTINEL, dtype=torch.float32, device=DEV)
+    call("sed_median_filter_k", x_d, buf, h2d(list(sizes), torch.int32, x_d.device), scale_d, B, T, C, mode, max_size)
+    got = buf.cpu().numpy()
+    return got[:B * T * C].reshape(B, T, C), got[B * T * C:]
+
+
+NAN_SIZES = [24, 5, 33]                                 # bound 33 at T = 256: the global-rank form, the 5-frame window riding along
+NAN_ROWS = [[24, 5, 33], [5, 33, 24], [33, 24, 5]]
+NAN_AT = ((1, 0), (0, 1))                               # (clip, class)
+
+
+def _nan_case(partly=False):
+    """-> (x finite, x under test, scale finite, scale under test, bad [B, C]) at [2, 256, 3]: NaN enters the two (clip, class) columns
+    of NAN_AT through `scale` (the weak mask's route), or, `partly`, as every 7th frame of the input."""
+    B, T, C = 2, 256, 3
+    x = SC.bank_input(B, T, C, seed=4)
+    scale = (np.random.RandomState(4).randint(1, 9, size=(B, C)) / 8).astype(np.float32)
+    x_bad, scale_bad, bad = x.copy(), scale.copy(), np.zeros((B, C), dtype=bool)
+    for b, c in NAN_AT:
+        bad[b, c] = True
+        if partly:
+            x_bad[b, ::7, c] = np.nan
+        else:
+            scale_bad[b, c] = np.nan
+    return x, x_bad, scale, scale_bad, bad
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_nan_column_is_a_nan_column_in_the_clip_kernel(mode):
+    """A (clip, class) column that is all NaN (a fully padded clip's NaN weak posterior as `scale`) comes out all NaN from the global-rank
+    form; every other column holds the bits of the same launch with a finite scale; nothing is written behind the buffer.  NaN is the
+    references' own answer: `scipy.ndimage.median_filter` of an all-NaN line and `torch.median` of one both give NaN (checked on the
+    host).  Payload bits are not compared."""
+    x, _, scale, scale_bad, bad = _nan_case()
+    x_d = torch.from_numpy(x).to(DEV)
+    want, _ = _launch_clip(x_d, NAN_SIZES, mode, torch.from_numpy(scale).to(DEV), 33)
+    got, guard = _launch_clip(x_d, NAN_SIZES, mode, torch.from_numpy(scale_bad).to(DEV), 33)
+    assert np.all(guard == SENTINEL)
+    sel = np.broadcast_to(bad[:, None, :], got.shape)
+    assert np.isnan(got[sel]).all() and not np.isnan(want).any()
+    assert np.array_equal(_bits(got[~sel]), _bits(want[~sel]))
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_nan_column_is_a_nan_column_in_the_bank(mode):
+    """The same through the bank, three rows over the same windows: NaN where the column is NaN, the finite launch's bits elsewhere."""
+    x, _, scale, scale_bad, bad = _nan_case()
+    x_d = torch.from_numpy(x).to(DEV)
+    want, _ = _launch_bank(x_d, NAN_ROWS, mode, torch.from_numpy(scale).to(DEV), 33)
+    got, guard = _launch_bank(x_d, NAN_ROWS, mode, torch.from_numpy(scale_bad).to(DEV), 33)
+    assert np.all(guard == SENTINEL)
+    sel = np.broadcast_to(bad[None, :, None, :], got.shape)
+    assert np.isnan(got[sel]).all() and not np.isnan(want).any()
+    assert np.array_equal(_bits(got[~sel]), _bits(want[~sel]))
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_partly_nan_column_stays_inside_its_buffers(mode):
+    """Every 7th frame of two columns NaN: their values are unspecified (colliding ranks); the launches return, write nothing behind
+    their buffers and leave the NaN-free columns bit-equal to the finite launch."""
+    x, x_bad, scale, _, bad = _nan_case(partly=True)
+    x_d, bad_d, scale_d = torch.from_numpy(x).to(DEV), torch.from_numpy(x_bad).to(DEV), torch.from_numpy(scale).to(DEV)
+    want, _ = _launch_clip(x_d, NAN_SIZES, mode, scale_d, 33)
+    got, guard = _launch_clip(bad_d, NAN_SIZES, mode, scale_d, 33)
+    sel = np.broadcast_to(bad[:, None, :], got.shape)
+    assert np.all(guard == SENTINEL) and np.array_equal(_bits(got[~sel]), _bits(want[~sel]))
+    want, _ = _launch_bank(x_d, NAN_ROWS, mode, scale_d, 33)
+    got, guard = _launch_bank(bad_d, NAN_ROWS, mode, scale_d, 33)
+    sel = np.broadcast_to(bad[None, :, None, :], got.shape)
+    assert np.all(guard == SENTINEL) and np.array_equal(_bits(got[~sel]), _bits(want[~sel]))
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_clip_kernel_window_above_the_bound_is_a_nan_plane(mode):
+    """Device sizes [5, 80, 7] under a bound of 30 at T = 300 (the global-rank form; 300 + 79 entries exceed its 11-word bitmaps): class 1
+    comes out as NaN, classes 0 and 2 equal the host reference.  The bank's `test_window_out_of_range_is_a_nan_plane`, for the clip kernel."""
+    B, T, C = 2, 300, 3
+    x = SC.bank_input(B, T, C)
+    got, guard = _launch_clip(torch.from_numpy(x).to(DEV), [5, 80, 7], mode, None, 30)
+    assert np.all(guard == SENTINEL)
+    assert np.isnan(got[:, :, 1]).all()
+    want = SC.bank_ref(x, [[5, 5, 7]], mode)[0]
+    assert np.array_equal(got[:, :, [0, 2]], want[:, :, [0, 2]])
 
 
 def test_bad_arguments_write_nothing():

@@ -231,15 +231,18 @@ def test_bank_abi_header_library_and_build():
     proto = re.search(r"int\s+sed_median_filter_bank\s*\(([^)]*)\)\s*;", header, flags=re.S).group(1)
     assert " ".join(proto.split()).endswith("hipStream_t stream")
     assert int(re.search(r"#define\s+SED_HIP_ABI_VERSION\s+(\d+)", header).group(1)) == 7
-    assert "filter_bank.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "filter_bank.hip"))
+    assert "median_filter.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "median_filter.hip"))
     dll = ctypes.CDLL(build.build(verbose=False))
     assert hasattr(dll, "sed_median_filter_bank") and dll.sed_abi_version(0) == 7
-    src = open(os.path.join(build.CSRC, "filter_bank.hip")).read()
+    src = open(os.path.join(build.CSRC, "median_filter.hip")).read()
     assert int(re.search(r"#define\s+FB_MAX_W\s+(\d+)", src).group(1)) == pkg.filter.FILTER_BANK_MAX_ROWS == 64
-    front = open(os.path.join(build.CSRC, "frontend.hip")).read()                     # the dispatch the bank follows
-    assert int(re.search(r"#define\s+FB_RANK_MAXN\s+(\d+)", src).group(1)) == int(re.search(r"#define\s+MEDR_MAXN\s+(\d+)", front).group(1))
-    assert "max_size >= 24 && T >= 256 && T + max_size + 1 <= MEDR_MAXN" in front
-    assert (int(re.search(r"#define\s+FB_RANK_MIN\s+(\d+)", src).group(1)), int(re.search(r"#define\s+FB_RANK_MIN_T\s+(\d+)", src).group(1))) == (24, 256)
+    # the dispatch the bank follows is the clip filter's by construction: one predicate over one set of constants, stated once
+    core = open(os.path.join(build.CSRC, "median_select.h")).read()
+    consts = [int(re.search(rf"#define\s+{n}\s+(\d+)", core).group(1)) for n in ("MEDSEL_RANK_MIN", "MEDSEL_RANK_MIN_T", "MEDSEL_MAXN")]
+    assert consts == [24, 256, 2048]
+    assert "mode != 2 && max_size >= MEDSEL_RANK_MIN && T >= MEDSEL_RANK_MIN_T && T + max_size + 1 <= MEDSEL_MAXN" in core
+    assert src.count("if (medsel_use_ranks(mode, T, max_size))") == 2 and not re.search(r"max_size\s*>=\s*\d", src)
+    assert not any(re.search(rf"#define\s+{n}\b", src) for n in ("FB_RANK_MIN", "FB_RANK_MIN_T", "FB_RANK_MAXN", "MEDR_MAXN"))
 
 
 def test_filter_bank_refuses_on_the_host_first():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Post-processing search timing (transformer4sed_amd/postproc_search.py, csrc/filter_bank.hip); developer tool, needs a GPU.
+"""Post-processing search timing (transformer4sed_amd/postproc_search.py, csrc/median_filter.hip); developer tool, needs a GPU.
 
   1. The filter bank against one `sed_median_filter_k` launch per candidate row (each under its own bound, as `filter._run` calls it: what a
      loop over candidates costs without the bank), on [32, 1000, C] posteriors: the search's nine default windows (6 .. 179 frames) with

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsed_hip.so")
 SOURCES = ["gemm.hip", "gemm_tn.hip", "layout.hip", "attention.hip", "relpos_attention.hip", "norm_elem.hip", "frontend.hip", "pmam.hip", "cnn_branch.hip", "lora.hip", "dw_narrow.hip", "dasm.hip", "metrics.hip",
-           "conformer.hip", "fpool_transformer.hip", "fdy_cnn.hip", "grad_clip.hip", "gmm.hip", "psds.hip", "event_f1.hip", "longform.hip", "filter_bank.hip", "sebb.hip", "segment_pool.hip", "ensemble.hip"]
+           "conformer.hip", "fpool_transformer.hip", "fdy_cnn.hip", "grad_clip.hip", "gmm.hip", "psds.hip", "event_f1.hip", "longform.hip", "median_filter.hip", "sebb.hip", "segment_pool.hip", "ensemble.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # -ffast-math (re-association, approximate division / sqrt) only where MFMA operand rounding dominates the error anyway: the GEMM
 # epilogues, the attention softmax and the PMAM branch (16-bit NHWC activations): pmam.hip and the three sources split from it, the

@@ -1,4 +1,4 @@
-// Log-mel frontend, spectrogram augmentation and median-filter post-processing (HBM-bound kernels), gfx950.
+// Log-mel frontend, spectrogram augmentation and resampling (HBM-bound kernels), gfx950.
 //
 // Frontend replaces PasstFeatureExtractor (src/models/passt/passt_feature_extraction.py:46-94): per-clip max-abs
 // normalisation, pre-emphasis, centred/reflect-padded STFT (n_fft 1024, hop 320, symmetric Hann 800), power,
@@ -673,148 +673,6 @@ extern "C" int sed_add_noise(const float* x, const float* noise, const float* sn
     hipLaunchKernelGGL(clip_stats_kernel, dim3(NOISE_CHUNKS, B), dim3(256), 0, stream, x, part, n);
     hipLaunchKernelGGL(add_noise_kernel, dim3(64, B), dim3(256), 0, stream, x, noise, snr_lin, part, out, n);
     return sed_check_launch();
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Median / max filter along time per class, both reference semantics, bit-exact (compare/select only).
-//   mode 0: src/postprocess/filter.py:4-36   even size -> size+1, replicate padding, true median
-//   mode 1: scipy.ndimage.median_filter as called at src/codec/decoder.py:91: window [i - k/2, i - k/2 + k),
-//           symmetric (edge-inclusive reflect) padding, element of rank k/2
-//   mode 2: scipy.ndimage.maximum_filter (decoder.py:94), same window/padding
-// in/out [B, T, C]; one workgroup per (b, c).  Optional per-(b,c) multiplier applied first (soft weak mask,
-// decoder.py:80) or hard zeroing (decoder.py:22-23) via `scale` [B, C].
-// ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void median_filter_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                            const int* __restrict__ sizes, const float* __restrict__ scale,
-                                                            int T, int C, int mode) {
-    extern __shared__ float col[];  // [T]
-    const int b = blockIdx.x / C, c = blockIdx.x - b * C;
-    const float sc = scale != nullptr ? scale[b * C + c] : 1.0f;
-    for (int t = threadIdx.x; t < T; t += 256) {
-        const float v = in[((size_t)b * T + t) * C + c];
-        col[t] = scale != nullptr ? v * sc : v;
-    }
-    __syncthreads();
-    int k = sizes[c];
-    if (mode == 0 && (k & 1) == 0) k += 1;
-    const int lo = k / 2, rank = k / 2;
-    for (int i = threadIdx.x; i < T; i += 256) {
-        float res = 0.f;
-        if (mode == 2) {
-            float m = -INFINITY;
-            for (int j = 0; j < k; ++j) {
-                int idx = i - lo + j;
-                idx = idx < 0 ? -idx - 1 : (idx >= T ? 2 * T - idx - 1 : idx);
-                m = fmaxf(m, col[idx]);
-            }
-            res = m;
-        } else {
-            for (int a = 0; a < k; ++a) {
-                int ia = i - lo + a;
-                if (mode == 0) ia = ia < 0 ? 0 : (ia >= T ? T - 1 : ia);
-                else ia = ia < 0 ? -ia - 1 : (ia >= T ? 2 * T - ia - 1 : ia);
-                const float va = col[ia];
-                int lt = 0, le = 0;
-                for (int j = 0; j < k; ++j) {
-                    int ij = i - lo + j;
-                    if (mode == 0) ij = ij < 0 ? 0 : (ij >= T ? T - 1 : ij);
-                    else ij = ij < 0 ? -ij - 1 : (ij >= T ? 2 * T - ij - 1 : ij);
-                    const float vj = col[ij];
-                    lt += vj < va;
-                    le += vj <= va;
-                }
-                if (lt <= rank && rank < le) { res = va; break; }
-            }
-        }
-        out[((size_t)b * T + i) * C + c] = res;
-    }
-}
-// The same median (modes 0 and 1) for long windows -- the evaluation path filters with 32 / 128 frames (train.py:221-227: median_window
-// / 156 * 1000), where the rank search above is O(k^2) per output (4.5 ms per launch, 7 % of a validation batch).  Order statistics
-// on GLOBAL ranks instead: the padded column (T + k - 1 entries, padding entries kept as entries of their own, so every window is a
-// contiguous run of distinct entries) gets a total order once (rank = entries smaller, ties by position: n^2 / 256 compares per
-// thread); a window is then a bitmap over ranks, its median the (k/2 + 1)-th set bit, and sliding the window by one output clears one bit
-// and sets one.  The result is the same element the rank search returns (an input value, never an arithmetic combination): bit-exact.
-#define MEDR_MAXN 2048
-__global__ __launch_bounds__(256) void median_filter_rank_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                                 const int* __restrict__ sizes, const float* __restrict__ scale,
-                                                                 int T, int C, int mode, int W) {
-    extern __shared__ unsigned char medr_lds[];
-    float* vp = reinterpret_cast<float*>(medr_lds);                                  // [MEDR_MAXN] padded column
-    float* byrank = vp + MEDR_MAXN;                                                   // [MEDR_MAXN] value of rank r
-    unsigned short* rk = reinterpret_cast<unsigned short*>(byrank + MEDR_MAXN);      // [MEDR_MAXN] rank of padded entry p
-    unsigned* bm = reinterpret_cast<unsigned*>(rk + MEDR_MAXN);                      // [256][W] per-thread window bitmaps (W odd)
-    const int b = blockIdx.x / C, c = blockIdx.x - b * C, tid = threadIdx.x;
-    const float sc = scale != nullptr ? scale[b * C + c] : 1.0f;
-    int k = sizes[c];
-    if (mode == 0 && (k & 1) == 0) k += 1;
-    const int lo = k / 2, rank = k / 2, n = T + k - 1;
-    if (n > MEDR_MAXN || n > 32 * W) __builtin_trap();      // a window larger than the caller's bound: fail loudly, never silently
-    for (int p = tid; p < n; p += 256) {
-        int s_ = p - lo;
-        if (mode == 0) s_ = s_ < 0 ? 0 : (s_ >= T ? T - 1 : s_);
-        else s_ = s_ < 0 ? -s_ - 1 : (s_ >= T ? 2 * T - s_ - 1 : s_);
-        const float v = in[((size_t)b * T + s_) * C + c];
-        vp[p] = scale != nullptr ? v * sc : v;
-    }
-    __syncthreads();
-    for (int p = tid; p < n; p += 256) {
-        const float v = vp[p];
-        int r = 0;
-        for (int q = 0; q < n; ++q) {
-            const float u = vp[q];
-            r += (u < v) || (u == v && q < p);
-        }
-        rk[p] = (unsigned short)r;
-        byrank[r] = v;
-    }
-    __syncthreads();
-    const int chunk = (T + 255) / 256, i0 = tid * chunk;
-    if (i0 >= T) return;
-    unsigned* my = bm + tid * W;
-    for (int w = 0; w < W; ++w) my[w] = 0u;
-    for (int j = 0; j < k; ++j) { const int r = rk[i0 + j]; my[r >> 5] |= 1u << (r & 31); }
-    const int i1 = i0 + chunk < T ? i0 + chunk : T;
-    for (int i = i0; i < i1; ++i) {
-        int cum = 0, w = 0;
-        unsigned x = my[0];
-        int cnt = __popc(x);
-        while (cum + cnt <= rank) { cum += cnt; x = my[++w]; cnt = __popc(x); }
-        for (int t = rank - cum; t > 0; --t) x &= x - 1;          // drop the lower set bits: the wanted one becomes the lowest
-        out[((size_t)b * T + i) * C + c] = byrank[32 * w + __ffs(x) - 1];
-        if (i + 1 < i1) {
-            const int r0 = rk[i], r1 = rk[i + k];
-            my[r0 >> 5] &= ~(1u << (r0 & 31));
-            my[r1 >> 5] |= 1u << (r1 & 31);
-        }
-    }
-}
-static int median_filter_impl(const float* in, float* out, const int* sizes, const float* scale, int B, int T, int C, int mode,
-                              int max_size, hipStream_t stream) {
-    (void)hipGetLastError();
-    if (mode < 0 || mode > 2 || T > 12288 || max_size < 0) return SED_ERR_ARG;
-    // max_size: the caller's bound on the window sizes (they live on the device); 0 = unknown -> the rank-search kernel
-    if (mode != 2 && max_size >= 24 && T >= 256 && T + max_size + 1 <= MEDR_MAXN) {
-        int W = (T + max_size + 1 + 31) / 32;
-        W |= 1;                                     // odd row stride: the 64 lanes' bitmap words fall into different banks
-        const size_t lds = (size_t)MEDR_MAXN * (4 + 4 + 2) + (size_t)256 * W * 4;
-        static size_t attr = 0;
-        if (lds > attr) { (void)hipFuncSetAttribute((const void*)median_filter_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = lds; }
-        hipLaunchKernelGGL(median_filter_rank_kernel, dim3(B * C), dim3(256), lds, stream, in, out, sizes, scale, T, C, mode, W);
-        return sed_check_launch();
-    }
-    hipLaunchKernelGGL(median_filter_kernel, dim3(B * C), dim3(256), T * sizeof(float), stream, in, out, sizes, scale, T,
-                       C, mode);
-    return sed_check_launch();
-}
-extern "C" int sed_median_filter(const float* in, float* out, const int* sizes, const float* scale, int B, int T, int C,
-                                 int mode, hipStream_t stream) {
-    return median_filter_impl(in, out, sizes, scale, B, T, C, mode, 0, stream);
-}
-// the same filter with the caller's bound on the (device-resident) window sizes: long windows take the rank kernel
-extern "C" int sed_median_filter_k(const float* in, float* out, const int* sizes, const float* scale, int B, int T, int C,
-                                   int mode, int max_size, hipStream_t stream) {
-    return median_filter_impl(in, out, sizes, scale, B, T, C, mode, max_size, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------

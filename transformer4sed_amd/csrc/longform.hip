@@ -5,7 +5,7 @@
 //
 //   sed_longform_gather        wav [L] -> chunks [nk, Lc], chunk j from sample (k0 + j) hop on, zeros from L on
 //   sed_longform_stitch        strong [K, C, Tc] (x weak [K, C]) -> timeline [Tt, C]: triangular-capped weighted mean of the covering chunks
-//   sed_longform_filter        timeline [T, C] -> [T, C]: the filters of frontend.hip (same three modes, same element selected) on a
+//   sed_longform_filter        timeline [T, C] -> [T, C]: the filters of median_filter.hip (same three modes, same element selected) on a
 //                              timeline of any length, tiled along T with a halo of real neighbours
 //   sed_longform_event_count / sed_longform_event_write     timeline [T, C] > th [C] -> the maximal runs as (class, onset, offset) rows,
 //                              class-major, onsets ascending; two passes so the list is allocated at its exact size
@@ -13,6 +13,7 @@
 // Every loop is bounded by its sizes; no kernel waits for another workgroup, none uses a floating-point atomic: every output element is
 // computed by one thread from its sources in a fixed order, so results do not change from run to run.
 #include "common.h"
+#include "median_select.h"
 
 // --------------------------------------------------------------------------------------------------- chunk gather
 // One thread per four output samples.  VEC: wav, out, hop and Lc are all 16-byte multiples, so source and destination of a float4 are
@@ -109,23 +110,19 @@ extern "C" int sed_longform_stitch(const float* strong, const float* weak, float
 }
 
 // --------------------------------------------------------------------------------------------------- long filter
-// The three filters of frontend.hip (mode 0: median_filter_torch, even size -> size + 1, replicate padding; mode 1 / 2: scipy median /
+// The three filters of median_filter.hip (mode 0: median_filter_torch, even size -> size + 1, replicate padding; mode 1 / 2: scipy median /
 // maximum filter, window [i - k/2, i - k/2 + k), edge-inclusive reflection) on in / out [T, C] with any T.  One workgroup per (tile of
 // LF_TILE frames, class): the tile with k - 1 halo frames goes to LDS as the PADDED segment vp[0 .. n), n = frames + k - 1, where
 // vp[p] is frame t0 + p - k/2 -- a real neighbour wherever one exists; the boundary rule applies at frames < 0 and >= T only, the two
-// true ends of the timeline.  The window of local output i is then vp[i .. i + k).  Selection, as in frontend.hip and therefore
-// bit-identical to it: windows below 24 frames by rank search in window order, longer ones by global ranks of the segment (ties by
-// position) and a per-thread bitmap over ranks that slides with the window; the maximum by fmaxf in window order.
+// true ends of the timeline.  The window of local output i is then vp[i .. i + k).  Selection by median_select.h, as in median_filter.hip
+// and therefore bit-identical to it: windows below 24 frames by rank search in window order, longer ones by global ranks of the segment
+// (ties by position) and a per-thread bitmap over ranks that slides with the window; the maximum by fmaxf in window order.
 #define LF_TILE 1024
 #define LF_MAXN 2048                     // frames + halo of one tile: windows up to LF_MAXN - LF_TILE + 1 = 1025 frames
-#define LF_RANK_MIN 24
 __global__ __launch_bounds__(256) void lf_filter_kernel(const float* __restrict__ in, float* __restrict__ out, const int* __restrict__ sizes,
                                                         long long T, int C, int mode, int max_k, int W) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lf_lds[];
-    float* vp = reinterpret_cast<float*>(lf_lds);                                    // [LF_MAXN] padded segment
-    float* byrank = vp + LF_MAXN;                                                     // [LF_MAXN] value of rank r
-    unsigned short* rk = reinterpret_cast<unsigned short*>(byrank + LF_MAXN);        // [LF_MAXN] rank of padded entry p
-    unsigned* bm = reinterpret_cast<unsigned*>(rk + LF_MAXN);                        // [256][W] per-thread window bitmaps (W odd)
+    const MedselLds s = medsel_carve(lf_lds, LF_MAXN);                               // (byrank, rk, bm: launches with long windows only; W odd)
     const int tid = threadIdx.x;
     const int c = blockIdx.x % C;                     // class fastest: the workgroups in flight together share the lines they read
     const long long t0 = (long long)(blockIdx.x / C) * LF_TILE;
@@ -137,70 +134,27 @@ __global__ __launch_bounds__(256) void lf_filter_kernel(const float* __restrict_
         for (int i = tid; i < len; i += 256) out[(size_t)(t0 + i) * C + c] = __builtin_nanf("");
         return;
     }
-    const int lo = k / 2, rank = k / 2, n = len + k - 1;
+    const int lo = k / 2, n = len + k - 1;
     for (int p = tid; p < n; p += 256) {
-        long long s = t0 + p - lo;
-        if (mode == 0) s = s < 0 ? 0 : (s >= T ? T - 1 : s);
-        else s = s < 0 ? -s - 1 : (s >= T ? 2 * T - s - 1 : s);
-        s = s < 0 ? 0 : (s >= T ? T - 1 : s);         // (reflection is single for k <= T, which the caller checks; this keeps any k in bounds)
-        vp[p] = in[(size_t)s * C + c];
+        long long f = medsel_src(t0 + p - lo, T, mode);
+        f = f < 0 ? 0 : (f >= T ? T - 1 : f);         // (reflection is single for k <= T, which the caller checks; this keeps any k in bounds)
+        s.vp[p] = in[(size_t)f * C + c];
     }
     __syncthreads();
+    float* o = out + (size_t)t0 * C + c;
     if (mode == 2) {
-        for (int i = tid; i < len; i += 256) {
-            float m = -INFINITY;
-            for (int j = 0; j < k; ++j) m = fmaxf(m, vp[i + j]);
-            out[(size_t)(t0 + i) * C + c] = m;
-        }
+        for (int i = tid; i < len; i += 256) o[(size_t)i * C] = medsel_window_max([&](int j) { return s.vp[i + j]; }, k);
         return;
     }
-    if (k < LF_RANK_MIN) {
-        for (int i = tid; i < len; i += 256) {
-            float res = 0.f;
-            for (int a = 0; a < k; ++a) {
-                const float va = vp[i + a];
-                int lt = 0, le = 0;
-                for (int j = 0; j < k; ++j) {
-                    const float vj = vp[i + j];
-                    lt += vj < va;
-                    le += vj <= va;
-                }
-                if (lt <= rank && rank < le) { res = va; break; }
-            }
-            out[(size_t)(t0 + i) * C + c] = res;
-        }
+    if (k < MEDSEL_RANK_MIN) {
+        for (int i = tid; i < len; i += 256) o[(size_t)i * C] = medsel_rank_search([&](int j) { return s.vp[i + j]; }, k);
         return;
     }
-    for (int p = tid; p < n; p += 256) {
-        const float v = vp[p];
-        int r = 0;
-        for (int q = 0; q < n; ++q) {
-            const float u = vp[q];
-            r += (u < v) || (u == v && q < p);
-        }
-        rk[p] = (unsigned short)r;
-        byrank[r] = v;
-    }
+    medsel_rank_column(s.vp, n, s.rk, s.byrank);
     __syncthreads();
     const int chunk = (len + 255) / 256, i0 = tid * chunk;
     if (i0 >= len) return;
-    unsigned* my = bm + tid * W;
-    for (int w = 0; w < W; ++w) my[w] = 0u;
-    for (int j = 0; j < k; ++j) { const int r = rk[i0 + j]; my[r >> 5] |= 1u << (r & 31); }
-    const int i1 = i0 + chunk < len ? i0 + chunk : len;
-    for (int i = i0; i < i1; ++i) {
-        int cum = 0, w = 0;
-        unsigned x = my[0];
-        int cnt = __popc(x);
-        while (cum + cnt <= rank) { cum += cnt; x = my[++w]; cnt = __popc(x); }
-        for (int q = rank - cum; q > 0; --q) x &= x - 1;          // drop the lower set bits: the wanted one becomes the lowest
-        out[(size_t)(t0 + i) * C + c] = byrank[32 * w + __ffs(x) - 1];
-        if (i + 1 < i1) {
-            const int r0 = rk[i], r1 = rk[i + k];
-            my[r0 >> 5] &= ~(1u << (r0 & 31));
-            my[r1 >> 5] |= 1u << (r1 & 31);
-        }
-    }
+    medsel_slide(s.rk, s.byrank, s.bm + tid * W, W, k, i0, i0 + chunk < len ? i0 + chunk : len, o, C);
 }
 extern "C" int sed_longform_filter(const float* in, float* out, const int* sizes, int64_t T, int C, int mode, int max_size,
                                    hipStream_t stream) {
@@ -212,10 +166,9 @@ extern "C" int sed_longform_filter(const float* in, float* out, const int* sizes
     const int64_t nwg = (T + LF_TILE - 1) / LF_TILE * C;
     if (nwg > 0x7fffffffLL) return SED_ERR_ARG;
     const int n_max = (T < LF_TILE ? (int)T : LF_TILE) + max_k - 1;
-    int W = (n_max + 31) / 32;
-    W |= 1;                                          // odd row stride: the 64 lanes' bitmap words fall into different banks
-    const bool ranks = mode != 2 && max_k >= LF_RANK_MIN;
-    const size_t lds = ranks ? (size_t)LF_MAXN * (4 + 4 + 2) + (size_t)256 * W * 4 : (size_t)LF_MAXN * 4;
+    const int W = medsel_bitmap_stride(n_max);
+    const bool ranks = mode != 2 && max_k >= MEDSEL_RANK_MIN;      // (the kernel chooses per class: k >= MEDSEL_RANK_MIN)
+    const size_t lds = ranks ? medsel_rank_lds(LF_MAXN, W) : (size_t)LF_MAXN * 4;
     static size_t attr = 0;
     if (lds > attr) { (void)hipFuncSetAttribute((const void*)lf_filter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = lds; }
     hipLaunchKernelGGL(lf_filter_kernel, dim3((unsigned)nwg), dim3(256), lds, stream, in, out, sizes, (long long)T, C, mode, max_k, W);

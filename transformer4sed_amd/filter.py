@@ -40,7 +40,7 @@ def max_filter_scipy(scores, filter_size, weak_scale=None):
     return _run(scores, filter_size, 2, weak_scale)
 
 
-FILTER_BANK_MAX_ROWS = 64      # csrc/filter_bank.hip: window rows of one launch
+FILTER_BANK_MAX_ROWS = 64      # csrc/median_filter.hip: window rows of one launch
 
 
 def check_bank_sizes(sizes, T, C, mode):
@@ -63,7 +63,7 @@ def check_bank_sizes(sizes, T, C, mode):
 def filter_bank(x, sizes, mode, scale=None):
     """x [B, T, C], sizes [W][C] -> [W, B, T, C]: out[w] is bit for bit what `sed_median_filter_k` writes for the row sizes[w] under the
     bank's bound (the largest window of all rows) -- the values of `_run(x, sizes[w], mode, scale)` -- all W rows from one launch that
-    stages and ranks every (clip, class) column once (csrc/filter_bank.hip)."""
+    stages and ranks every (clip, class) column once (csrc/median_filter.hip)."""
     if x.dim() != 3:
         raise ValueError("input_tensor must have shape (Batch, Length, Classes)")
     B, T, C = x.shape

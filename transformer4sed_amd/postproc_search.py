@@ -3,7 +3,7 @@ lists which threshold, gives each class its best PSDS or F1 on a validation set.
 
 The reference ships its per-class windows (`median_window: [5,20,5,5,5,20,20,20,5,20]`, `filter_type`) tuned by hand; here they are searched:
 every batch of validation posteriors is filtered with ALL candidate windows by one launch per filter type (`filter.filter_bank`,
-csrc/filter_bank.hip: a column is staged and ranked once for the whole bank), each candidate's slice feeds an accumulator of its own
+csrc/median_filter.hip: a column is staged and ranked once for the whole bank), each candidate's slice feeds an accumulator of its own
 (`IntersectionPSDS` per filter type, candidate and argument set; `EventSegmentF1` per threshold and candidate), and the choice is made per
 class at the end.  A class's single-class PSDS and its class-wise F1 depend on that class's scores alone -- the cross-trigger term of psds2
 counts that class's detections against the other classes' GROUND TRUTH -- so the per-class choice is exact, and the value of the mixed choice
